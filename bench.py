@@ -11,8 +11,16 @@ value = CV-grid wall-clock (seconds per grid, max over ranks; lower is better). 
 rates ride along in `config`: all fit-iterations / s, and the Gram-forming ones (fit-iterations
 whose own X^T W X was computed) / s.
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no launcher it starts
-N rank processes itself (torch.distributed.run, 127.0.0.1) before touching the GPU.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].  With
+N > 1 and no launcher it starts N rank processes itself (torch.distributed.run, 127.0.0.1)
+before touching the GPU.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the
+legs that take runs of their own: the CPU baselines, the float64 Newton-distance spot check,
+the drop-in production flow and the host-frame (PCIe-inclusive) rates; --no-cpu / --no-check /
+--no-dropin drop single legs of a --full run.  --dump-outputs DIR writes what the last timed
+step returned to its caller as DIR/<name>.npy (float64; a fixed seeded sample where the whole
+output is larger than the cap), for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -71,6 +79,7 @@ SIGNAL_TRIALS = 60_000
 C5_RESPONSES = 64
 PREP_SHIFT = 1     # er_refactored_from_scratch_cleanup.py:269 calls preprocess_lynne(df, trial_shift_bounds=1)
 INIT_PASSES = 2
+DUMP_CAP_BYTES = 64 * 2 ** 20       # --dump-outputs: all files of one run together
 
 
 def parse():
@@ -81,15 +90,21 @@ def parse():
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 1; 3 for "
                     "designmat)")
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the timed steps: CPU baselines, the float64 "
+                         "Newton-distance check, the drop-in flow, host-frame rates")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the float64 Newton-distance spot check after the timed region "
-                         "(its rocBLAS kernels stay out of a kernel-trace profile)")
+                    help="--full: skip the float64 Newton-distance spot check after the timed "
+                         "region (its rocBLAS kernels stay out of a kernel-trace profile)")
     ap.add_argument("--cpu-full-fold", type=int, default=1,
                     help="1: the CPU baseline times one full-size split fit + refit (BASELINE.md "
                          "§2); 0: only the row sample")
     ap.add_argument("--no-dropin", action="store_true",
-                    help="skip the drop-in production-flow leg (dropin_grid_s)")
+                    help="--full: skip the drop-in production-flow leg (dropin_grid_s)")
     ap.add_argument("--cpu-rows", type=int, default=100_000,
                     help="rows of the oracle Newton sample (secondary CPU figure)")
     ap.add_argument("--sklearn-rows", type=int, default=100_000,
@@ -105,7 +120,44 @@ def parse():
         a.steps = 20 if short else 2
     if a.warmup is None:
         a.warmup = 3 if short else 1
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the legs beside the timed steps run only under --full
+    a.cpu = a.full and not a.no_cpu
+    a.check = a.full and not a.no_check
+    a.dropin = a.full and not a.no_dropin
     return a
+
+
+def sample_index(n, cap, seed=0):
+    """Every position of n when n <= cap, else a fixed (seeded) sorted sample of cap of them."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(a, arrays):
+    """--dump-outputs: {name: array or tensor} -> DIR/<name>.npy in float64 (rank 0 writes)."""
+    if not a.dump_outputs:
+        return
+    host = {}
+    for name, v in arrays.items():
+        v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        host[name] = np.ascontiguousarray(v, dtype=np.float64)
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_CAP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes "
+                         f"(cap {DUMP_CAP_BYTES})")
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), v)
+
+
+def grid_arrays(res):
+    """The per-parameter result dicts of one CV grid (grid.run's return) as stacked arrays."""
+    keys = ("cv_coefs", "cv_intercepts", "cv_scores_train", "cv_scores_test", "cv_R2_score",
+            "cv_mse_score", "refit_coef", "refit_intercept")
+    return {k: np.stack([np.asarray(r[k], dtype=np.float64) for r in res]) for k in keys}
 
 
 def dense_slice(s, rows):
@@ -293,8 +345,16 @@ def bench_c5(a):
         el = float(t[0])
     if rank != 0:
         return
+    if a.dump_outputs:
+        # every response's refit and scores; the split coefficients of a seeded 16 responses
+        per = [grid_arrays(o) for o in out]
+        arr = {k: np.stack([v[k] for v in per]) for k in per[0] if k != "cv_coefs"}
+        rs = sample_index(R, 16)
+        arr["cv_coefs_sample"] = np.stack([per[r]["cv_coefs"] for r in rs])
+        arr["cv_coefs_sample_responses"] = rs
+        dump_outputs(a, arr)
     cpu = None
-    if not a.no_cpu and world == 1:
+    if a.cpu and world == 1:
         cpu = cpu_reference_enet(s, Y, cv_idx, alphas, a.sklearn_rows, R, fits_total)
     achieved = cd_flop / (cd_ms * 1e-3) / 1e12
     print(json.dumps({
@@ -416,14 +476,20 @@ def bench_prep(a):
         el = float(t[0])
     if rank != 0:
         return
-    # host DataFrame columns in, host columns out: the PCIe-inclusive rate (never `value`)
-    t1 = time.perf_counter()
-    prep.session_columns(Xh, PREP_SHIFT)
-    pcie_s = time.perf_counter() - t1
+    if a.dump_outputs:
+        rows = sample_index(n, 100_000)
+        dump_outputs(a, {"derived_columns_sample": out[:, torch.from_numpy(rows).cuda()],
+                         "sample_rows": rows})
+    pcie_s = None
+    if a.full:
+        # host DataFrame columns in, host columns out: the PCIe-inclusive rate (never `value`)
+        t1 = time.perf_counter()
+        prep.session_columns(Xh, PREP_SHIFT)
+        pcie_s = time.perf_counter() - t1
     bytes_per_row = 8 * (len(prep.IN_COLS) + len(prep.OUT_COLS))
     achieved = bytes_per_row * n / (call_ms * 1e-3) / 1e9
     cpu = None
-    if not a.no_cpu:
+    if a.cpu:
         from oracle import prep_pandas
         rows = 2_000_000
         sub = {c: v[:rows] for c, v in cols.items()}
@@ -442,7 +508,7 @@ def bench_prep(a):
         "config": {"workload": f"one {n}-row behaviour session per rank (9 float64 event "
                                f"columns -> 40 derived columns, trial_shift_bounds {PREP_SHIFT} as the drivers call it)",
                    "config_name": "prep", "rows": n,
-                   "pcie_inclusive_rows_per_s": n / pcie_s,
+                   "pcie_inclusive_rows_per_s": n / pcie_s if pcie_s else None,
                    "parallelism": f"one session per rank, {world} rank(s)"},
         "roofline": {"bound": "hbm", "kernel": "sglm_prep_session (whole call: 7 row kernels + "
                                                "9 chunked scans)",
@@ -525,12 +591,24 @@ def bench_signal(a):
     # flag columns read, three count columns written, the row map (int64 + u8) per output row
     algo = 8 * nc * n + 8 * nr + 16 * n + 24 * n + 9 * n_out
     achieved = algo / (call_ms * 1e-3) / 1e9
-    t1 = time.perf_counter()
-    full, _ = G.signal_frame(sig, table)
-    e2e_s = time.perf_counter() - t1
-    assert len(full) == n_out
+    if a.dump_outputs:
+        rows = sample_index(n, 100_000)
+        rows_d = torch.from_numpy(rows).cuda()
+        orow = sample_index(n_out, 100_000, seed=1)
+        orow_d = torch.from_numpy(orow).cuda()
+        dump_outputs(a, {"aligned_columns_sample": out[:, rows_d],
+                         "trial_columns_sample": ws.cols[:, rows_d], "sample_rows": rows,
+                         "row_map_src_sample": ws.src[orow_d],
+                         "row_map_dup_sample": ws.dup[orow_d], "row_map_sample_rows": orow,
+                         "ncopies": ws.ncopies})
+    e2e_s = None
+    if a.full:
+        t1 = time.perf_counter()
+        full, _ = G.signal_frame(sig, table)
+        e2e_s = time.perf_counter() - t1
+        assert len(full) == n_out
     cpu = None
-    if not a.no_cpu:
+    if a.cpu:
         from oracle import signal_ref
         trials = 3000
         ssig, stab = synth.signal_session(trials, 200 + rank)
@@ -550,7 +628,7 @@ def bench_signal(a):
                                f"{nc} aligned columns, trial bounds -20 / +20, {n_out} output "
                                f"rows)",
                    "config_name": "signal", "rows": n,
-                   "dropin_host_frames_rows_per_s": n / e2e_s,
+                   "dropin_host_frames_rows_per_s": n / e2e_s if e2e_s else None,
                    "parallelism": f"one session per rank, {world} rank(s)"},
         "roofline": {"bound": "hbm", "kernel": "sglm_scatter_rows x5 + sglm_signal_trials "
                                                "(whole step: 17 launches)",
@@ -611,13 +689,19 @@ def bench_designmat(a):
     n_in = len([c for c in cols if c != "__order__"])
     algo_row = 8 * (n_in + K)                # every input column read once, the matrix written
     achieved = algo_row * n / el / 1e9
-    # the drop-in with host frames in and out (PCIe + pandas frame assembly), never `value`
-    t1 = time.perf_counter()
-    with contextlib.redirect_stdout(io.StringIO()):
-        pp_design_mat.make_design_mat(ts.copy(), tr, interactions=DM_INTERACTIONS)
-    e2e_s = time.perf_counter() - t1
+    if a.dump_outputs:
+        rows = sample_index(n, 100_000)
+        dump_outputs(a, {"design_block_sample": res.block[:, torch.from_numpy(rows).cuda()],
+                         "sample_rows": rows})
+    e2e_s = None
+    if a.full:
+        # the drop-in with host frames in and out (PCIe + pandas frame assembly), never `value`
+        t1 = time.perf_counter()
+        with contextlib.redirect_stdout(io.StringIO()):
+            pp_design_mat.make_design_mat(ts.copy(), tr, interactions=DM_INTERACTIONS)
+        e2e_s = time.perf_counter() - t1
     cpu = None
-    if not a.no_cpu:
+    if a.cpu:
         import warnings
         from oracle import designmat_pandas
         sts, str_ = synth.designmat_session(DM_CPU_TRIALS, 300 + rank)
@@ -640,7 +724,7 @@ def bench_designmat(a):
                                f"float64 input columns -> {K} design columns; interactions "
                                f"{DM_INTERACTIONS}, nth_licks [1])",
                    "config_name": "designmat", "rows": n, "columns": res.names,
-                   "dropin_host_frames_rows_per_s": n / e2e_s,
+                   "dropin_host_frames_rows_per_s": n / e2e_s if e2e_s else None,
                    "event_ms_per_step": call_ms,
                    "parallelism": f"one session per rank, {world} rank(s)"},
         "roofline": {"bound": "hbm", "kernel": "design_matrix_device (whole step: 2 groupings, "
@@ -749,7 +833,9 @@ def bench_ols(a):
     coef = np.asarray(best.model.coef_)
     # the synthetic truth is known: the refit recovers it to the noise level
     truth_err = float(np.max(np.abs(coef - beta.reshape(-1))))
-    cpu = None if a.no_cpu else cpu_reference_ols(df, ev, L, setup, cv_idx, K)
+    dump_outputs(a, {"best_coef": coef, "best_intercept": best.model.intercept_,
+                     "best_cv_R2": out[0], "holdout_R2": hs})
+    cpu = cpu_reference_ols(df, ev, L, setup, cv_idx, K) if a.cpu else None
     p = len(xcols)
     print(json.dumps({
         "metric": "IRLS iters/sec on 1M\u00d72000 design mat; CV-grid wall-clock (5-fold\u00d720 \u03bb)",
@@ -893,7 +979,8 @@ def bench_cb(a):
     coef = np.asarray(out[3].model.coef_)
     nl = len(ev) * (2 * L + 1)
     truth_err = float(np.max(np.abs(coef[:nl] - beta.reshape(-1))))
-    cpu = None if a.no_cpu else cpu_reference_cb(X_setup, y_setup, cv, K)
+    dump_outputs(a, {"best_coef": coef, "best_cv_R2": out[0], "holdout_R2": hs})
+    cpu = cpu_reference_cb(X_setup, y_setup, cv, K) if a.cpu else None
     print(json.dumps({
         "metric": "IRLS iters/sec on 1M\u00d72000 design mat; CV-grid wall-clock (5-fold\u00d720 \u03bb)",
         "value": el, "unit": "s per production workload (host frame -> fits -> holdout score)",
@@ -1151,13 +1238,14 @@ def main():
         gram_kernel = "lag_gram_w2_kernel" if E._lagw(design) is not None else "syrk6_kernel"
         traffic, traffic_src = pmc_traffic(gram_kernel)
         conv = all(r["converged"] for r in res)
+        dump_outputs(a, grid_arrays(res))
         ndist = None
-        if world == 1 and a.config in ("c4", "c4mixed") and not a.no_check:
+        if world == 1 and a.config in ("c4", "c4mixed") and a.check:
             # float64 Newton distance of the lambda = 1e-4 split-0 fit and refit (parity spot
             # check of the timed grid's output; tests/test_gpu_fullsize.py checks every fit)
             ndist = newton_distance(s, design, cv_idx, res, lams, [(0, 0), (0, -1)], extra)
         dropin = None
-        if world == 1 and a.config in ("c3", "c4") and not a.no_dropin:
+        if world == 1 and a.config in ("c3", "c4") and a.dropin:
             # the production flow through the drop-in API from a host event DataFrame (the
             # design stays on the device: sglm_hip.lagframe), one warm pass then timed passes
             df, ev = dropin_frame(s)
@@ -1181,7 +1269,7 @@ def main():
                                      "sglm_ez.timeshift_cols -> isna().sum(axis=1) == 0 row "
                                      "filter -> cv_idx_by_trial_id -> simple_cv_fit"}
         cpu = None
-        if not a.no_cpu and world == 1 and extra is None:
+        if a.cpu and world == 1 and extra is None:
             cpu = cpu_reference_grid(s, cv_idx, lams, a.sklearn_rows)
             if a.cpu_full_fold:
                 # the planned measurement: one full-size split fit + refit,

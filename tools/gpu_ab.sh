@@ -8,7 +8,7 @@ timeout -k 10 120 python -u tools/chol_bench.py > $O/chain_base.json 2> $O/chain
 env $KV timeout -k 10 120 python -u tools/chol_bench.py > $O/chain_var.json 2> $O/chain_var.err
 env $KV timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $O/tests_var.log 2>&1
 for rep in 1 2; do
-  timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu > $O/bench_base_$rep.json 2> $O/bench_base_$rep.err
-  env $KV timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu > $O/bench_var_$rep.json 2> $O/bench_var_$rep.err
+  timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu > $O/bench_base_$rep.json 2> $O/bench_base_$rep.err
+  env $KV timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu > $O/bench_var_$rep.json 2> $O/bench_var_$rep.err
 done
 env $KV timeout -k 10 300 python -u tools/rank_sim.py --world 8 --all > $O/rank8_var.json 2> $O/rank8_var.err

@@ -7,4 +7,4 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_sharded.py tests/test_gpu_d
 for w in 2 4 8; do
   timeout -k 10 300 python -u tools/rank_sim.py --mode rows --world $w --all > $O/rows$w.json 2> $O/rows$w.err
 done
-timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --no-cpu --steps 5 > $O/g2.json 2> $O/g2.err
+timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --no-cpu --steps 5 > $O/g2.json 2> $O/g2.err

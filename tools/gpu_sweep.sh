@@ -2,7 +2,7 @@
 set -e
 export TMPDIR=/tmp
 O=gpurun_out/sw; mkdir -p $O
-run() { timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu > $O/bench_$1.json 2> $O/bench_$1.err; }
+run() { timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu > $O/bench_$1.json 2> $O/bench_$1.err; }
 run base
 SGLM_IRLS_GROUPS=1 run g1
 SGLM_HESS_SHARE_TOL=0.75 run share075
