@@ -601,7 +601,11 @@ __global__ void __launch_bounds__(256) lag_gram_w_sym(float* __restrict__ H,
         }
         const int ki = ks_i[il], kj = ks_j[jl];
         if (i == j) {                            // diagonal: in place (H[p][p] by aux)
-            if (ki >= 0 && split(ki, ki, 63 - ki % 64)) *dst += Hbf[(int64_t)i * P + j];
+            if (ki >= 0) {
+                if (split(ki, ki, 63 - ki % 64)) *dst += Hbf[(int64_t)i * P + j];
+            } else if (i < p) {
+                *dst = 0.0f;                     // a continuous column's own diagonal entry
+            }
             continue;
         }
         if (j == p) {

@@ -1863,8 +1863,9 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 k_h.append(int(k))
             fkey[k] = keys[key]
         k_h = np.asarray(k_h, dtype=np.int32)
-        # the exact mask Gram of each (W = the mask's multiplicities; the first link update
-        # overwrites W)
+        # the exact mask Gram of each (W = the mask's multiplicities; the fit's first link update
+        # overwrites W -- a fit whose first link GRAD_DEDUP skips keeps them, which is why such
+        # a fit is never the Gram representative of its start key, see the lead choice there)
         kh_d = up(k_h, np.int64)
         bf.W[kh_d] = prob.M[up(fmask_h[k_h], np.int64)].float()
         _syrk(d, bf, k_h, nsteps, ntile1, None, st, exact=True, rows=gram_rows)
@@ -2023,8 +2024,18 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             # (hkey) have one predictor, hence bitwise one W, R and X^T R: the link and the
             # gradient run once per key and the other fits' gradient rows are copies (at C4:
             # 6 of 120 fits in the first iteration, where the factorisation chain runs beside
-            # the gradient); nothing else reads a copied fit's W or R before its next link
+            # the gradient).  A copied fit's R is not read before its next link, but its W is the
+            # Gram operand if hess_plan makes it the representative of its key -- the first fit
+            # of the key that is no cross-mask candidate, e.g. an unpenalised fit listed after
+            # penalised ones, whose W still holds the mask multiplicities of the rank Gram above
+            # -- so the lead is chosen by that rule: the first fit of the key that forms its
+            # own Hessian, else (all candidates: a failed one forms in this order) the first
+            own_ok = drift[act] <= reuse_tol
+            is_cand = (repl[act] >= 0) & ~no_alias[act] & ~own_ok
             lead_of, first = {}, {}
+            for k in act[~is_cand & ~own_ok]:
+                if fresh_start[k]:
+                    first.setdefault(hkey(k), int(k))
             for k in act:
                 if fresh_start[k]:
                     rk = first.setdefault(hkey(k), int(k))
@@ -3286,7 +3297,7 @@ def _lag_gram_w(d: Design, lg, bf, fits: np.ndarray, st, ev=None):
     # ~16 B per raw row per fit, and a P x P image per fit for the split pieces' second halves)
     # stays within LAGW_WORK_BUDGET: fits in chunks of at most that
     per1 = _lib.query("sglm_lag_gram_w_work_bytes", lg.n_raw, lg.K, 1, d.P)
-    chunk = max(1, min(nact, int(LAGW_WORK_BUDGET // max(1, per1))))
+    chunk = _lagw_chunk(lg.n_raw, lg.K, nact, per1, LAGW_WORK_BUDGET)
     work = _work(_lib.query("sglm_lag_gram_w_work_bytes", lg.n_raw, lg.K, chunk, d.P), d.device,
                  "lagw")
     with _GRAM_LOCK:
@@ -3306,6 +3317,16 @@ def _lag_gram_w(d: Design, lg, bf, fits: np.ndarray, st, ev=None):
     pa = d.p + 1
     return (8 * lg.n_raw + nact * (4 * lg.n + 4 * pa * (pa + 1) // 2), nact * lg.flop1,
             _lagw_exec_flop(lg, nact))
+
+
+def _lagw_chunk(n_raw: int, K: int, nact: int, per1: int, budget: float) -> int:
+    """Fits per sglm_lag_gram_w launch: as many of the nact as ``budget`` bytes of scratch hold
+    (per1 bytes per fit), and few enough that one weight copy stays within the launch's 32-bit
+    buffer offsets (csrc/lagw.hip, lagw_wlen: ((n_raw + 2K + 16) * fits + 519) / 8 * 8 elements,
+    refused from 2^27); at least one."""
+    chunk = max(1, min(int(nact), int(budget // max(1, per1))))
+    cap = ((1 << 27) - 520) // (int(n_raw) + 2 * int(K) + 16)
+    return max(1, min(chunk, cap))
 
 
 # bytes of sglm_lag_gram_w scratch one launch may use (its fits are split into launches beyond

@@ -433,6 +433,73 @@ def test_first_iteration_gradient_dedup(engine, monkeypatch):
         assert a["converged"] and b["converged"]
 
 
+def _lam0_after_penalised(monkeypatch, max_iter):
+    """A 3-fold Poisson grid whose objectives put alpha = 0 AFTER two penalised ones: on every
+    fold mask the penalised fits (cross-mask candidates, ahead in the fit table) share the
+    unpenalised fit's start key, and that fit is both a first-iteration Gram representative and
+    the holder of its mask's exact rank Gram (its W starts as the mask multiplicities).  Solved
+    with GRAD_DEDUP on and off; returns (synthetic, folds, on, off)."""
+    from sglm_hip import engine as E, folds, grid, synth
+    from sglm_hip.estimators import Objective
+    s = synth.make(N=30_000, m=12, L=8, family="poisson", rho=0.03)
+    codes = folds.trial_keys_codes(pd.DataFrame({"nTrial": s.trial}), ["nTrial"]).values
+    np.random.seed(3)
+    cv_idx = folds.cv_idx_from_bucket_ids(codes, num_folds=3)
+    # a Hessian formed from the multiplicities instead of the weights is off by mean(y): visible
+    # only when that is not 1
+    for tr, _ in cv_idx:
+        assert abs(np.mean(s.y[np.asarray(tr)]) - 1.0) > 0.2
+    d = E.Design.from_events(s.E, s.shifts, s.L - 1, s.N)
+    objs = [Objective("irls", E.FAM_TWEEDIE_LOG, 1.0, a, "n", True, max_iter)
+            for a in (1e-2, 1e-1, 0.0)]
+    st = E.IrlsStats()
+    on = grid.run(d, s.y, cv_idx, objs, [0] * 3, stats=st)
+    assert st.grad_dedup > 0 and st.rank_grams > 0          # both mechanisms ran
+    monkeypatch.setattr(E, "GRAD_DEDUP", False)
+    st0 = E.IrlsStats()
+    off = grid.run(d, s.y, cv_idx, objs, [0] * 3, stats=st0)
+    assert st0.grad_dedup == 0 and st0.rank_grams > 0
+    return s, cv_idx, on, off
+
+
+def test_gradient_dedup_lam0_after_penalised_one_step(engine, monkeypatch):
+    """One Newton step (max_iter = 1) with and without GRAD_DEDUP: the same W and Hessian per
+    fit, so the step differs only through the gradient's summation order (1e-6 relative, the
+    split-K tolerance of test_first_iteration_gradient_dedup).  A fit whose first Hessian is
+    formed from stale weights steps mean(y) times too far or too short."""
+    _, _, on, off = _lam0_after_penalised(monkeypatch, 1)
+    for j, (a, b) in enumerate(zip(on, off)):
+        ratio = np.linalg.norm(a["cv_coefs"], axis=0) / np.linalg.norm(b["cv_coefs"], axis=0)
+        print(f"\n[dedup one step] objective {j}: |coef on| / |coef off| per fold {ratio}, "
+              f"refit {np.linalg.norm(a['refit_coef']) / np.linalg.norm(b['refit_coef'])}")
+    for j, (a, b) in enumerate(zip(on, off)):
+        assert rel(a["cv_coefs"], b["cv_coefs"]) < 1e-6, j
+        assert rel(a["cv_intercepts"], b["cv_intercepts"]) < 1e-6, j
+        assert rel(a["refit_coef"], b["refit_coef"]) < 1e-6, j
+
+
+def test_gradient_dedup_lam0_after_penalised_converged(engine, monkeypatch):
+    """The same grid to convergence: GRAD_DEDUP changes neither the coefficients (1e-6) nor any
+    fit's iteration count, every fit converges, and the unpenalised split fits and refit match
+    the float64 Newton oracle on their own rows."""
+    s, cv_idx, on, off = _lam0_after_penalised(monkeypatch, 100)
+    for j, (a, b) in enumerate(zip(on, off)):
+        assert rel(a["cv_coefs"], b["cv_coefs"]) < 1e-6, j
+        assert rel(a["cv_intercepts"], b["cv_intercepts"]) < 1e-6, j
+        assert rel(a["refit_coef"], b["refit_coef"]) < 1e-6, j
+        assert list(a["n_iter"]) == list(b["n_iter"]), (j, a["n_iter"], b["n_iter"])
+        assert a["converged"] and b["converged"], j
+    X = s.dense_X()
+    for k, (tr, _) in enumerate(cv_idx):
+        tr = np.asarray(tr)
+        c, b0 = glm_ref.fit_tweedie_newton(X[tr], s.y[tr], 0.0, 1.0)
+        assert rel(on[2]["cv_coefs"][:, k], c) < TOL_POIS, k
+        assert abs(on[2]["cv_intercepts"][k] - b0) < TOL_POIS * max(1.0, abs(b0)), k
+    c, b0 = glm_ref.fit_tweedie_newton(X, s.y, 0.0, 1.0)
+    assert rel(on[2]["refit_coef"], c) < TOL_POIS
+    assert abs(on[2]["refit_intercept"] - b0) < TOL_POIS * max(1.0, abs(b0))
+
+
 def test_concurrent_chains_equal_one_chain(engine, monkeypatch):
     """A batch of new factorisations split over two concurrent chains (CHOL_SPLIT = 2, the
     default for >= CHOL_SPLIT_MIN) does per fit the arithmetic of one chain: a C3-shape
