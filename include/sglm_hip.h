@@ -116,7 +116,9 @@ int sglm_gemv_eta(const void* X, int32_t xtype, int64_t ld, int32_t P, int64_t n
  * Rp receives R as three bf16 pieces hi + mid + lo == R, bf16 [3][Bp][ld] with
  * Bp = ceil(B/32)*32, row q = launch row -- the operand of sglm_xtr_bits_packed.
  * deta (optional, with step[q]): first eta[k] += step[q] * deta[k] (the previous Newton
- * step's predictor update, fused), then the link on the updated eta. */
+ * step's predictor update, fused), then the link on the updated eta.
+ * W may be NULL: the weights are then not stored (eta, R and Rp are what they are with W
+ * given); sglm_link_weights writes them later from the eta this call leaves behind. */
 int sglm_link_update(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                      const int32_t* slots, float* eta, const float* Y, const uint8_t* M,
                      const int32_t* fit_resp, const int32_t* fit_mask, float* W, float* R,
@@ -129,6 +131,15 @@ int sglm_link_update_rp(int32_t family, float power, int64_t n, int64_t ld, int3
                         const int32_t* fit_resp, const int32_t* fit_mask, float* W, float* R,
                         void* Rp, int32_t Bp, const int32_t* rpos, const float* step,
                         const float* deta, sglm_stream_t stream);
+/* The weights of sglm_link_update alone, for launch row q's fit slot k = slots[q] (q when
+ * slots is NULL), q < B:  W[k][i] = M[m][i] * d2loss/deta2 at eta[k][i] for i < n, 0 for
+ * n <= i < ld -- the same expression, so bitwise the W the link writes from that eta.  Rows of
+ * W of other slots are not touched.  engine.irls links without W and calls this for the fits
+ * whose Gram is about to be formed. */
+int sglm_link_weights(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
+                      const int32_t* slots, const float* eta, const float* Y, const uint8_t* M,
+                      const int32_t* fit_resp, const int32_t* fit_mask, float* W,
+                      sglm_stream_t stream);
 
 /* G[k][a] = sum_i X[a][i] * R[k][i] (float64 out; f32 MFMA partial sums, fixed-order
  * float64 reduction over row chunks).  `work`: sglm_xtr_work_bytes(P, B, n). */
@@ -512,7 +523,15 @@ int sglm_mask_stats(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, i
 
 /* Line search: out[q][j] = sum_i M[m][i] * loss(y_i, eta_i + t[j] * deta_i) (float64),
  * for j < T, over fit slot k = slots[q] (q when slots is NULL), q < B.
- * `work`: sglm_rowsum_work_bytes(B, T, n). */
+ * `work`: sglm_rowsum_work_bytes(B, T, n).
+ * Poisson (log link, power 1) with t = {0, 1, 1/2, 1/4, 1/8}: the trials j >= 1 are summed as
+ * differences, out[q][j] = out[q][0] + sum_i M (mu_i (exp(t_j deta_i) - 1) - y_i t_j deta_i)
+ * with mu = expf(eta) and exp(t deta) - 1 from expm1f(deta / 8) and squarings (f32 factors,
+ * float64 terms and sums): out[q][j] - out[q][0], which is all a line search reads, is accurate
+ * relative to its own size (about 1.3e-6 of sum M (mu |exp(t deta) - 1| + |y t deta|)), and
+ * out[q][0] to f32 rounding of mu.  With deta = 0 the five outputs are bitwise equal.
+ * The sums are two-level and deterministic: block partials per 8192-row chunk, then one wave per
+ * output sums the chunks in a fixed order. */
 size_t sglm_rowsum_work_bytes(int32_t B, int32_t T, int64_t n);
 int sglm_loss_trials(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                      const int32_t* slots, const float* eta, const float* deta, const float* Y, const uint8_t* M,
@@ -542,7 +561,10 @@ int sglm_eta_axpy_max(int64_t n, int64_t ld, int32_t B, const float* step, const
 
 /* out[q] = max over the rows of mask fit_mask[a] of |eta[a][i] - eta[b][i]| for the fit pairs
  * (a, b) = (pairs[2q], pairs[2q+1]) of one mask (npairs floats, zeroed by the call).  engine.irls
- * lets fit b take its Hessian from fit a's Gram when this distance is within tolerance. */
+ * lets fit b take its Hessian from fit a's Gram when this distance is within tolerance.
+ * Pairs are processed in groups of four consecutive ones; a fit that also belongs to the
+ * previous pair of its group is read once, so callers list pairs sharing a fit next to each
+ * other.  The values do not depend on the order. */
 int sglm_eta_pair_absmax(int64_t n, int64_t ld, int32_t npairs, const int32_t* pairs,
                          const uint8_t* M, const int32_t* fit_mask, const float* eta,
                          float* out, sglm_stream_t stream);

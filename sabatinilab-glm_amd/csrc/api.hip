@@ -147,6 +147,8 @@ __global__ void __launch_bounds__(256) eta_kernel(const TX* __restrict__ X, int6
 // optional f32 R are written per slot; Rp (optional) receives R as three bf16 pieces
 // hi + mid + lo == R in the packed operand layout of the gradient kernel, row y of each piece
 // plane (Bp rows per plane): the split is fused here instead of a separate pass over R.
+// W may be null: the IRLS loop reads W only where a Gram is formed from it and has
+// link_weights_kernel write those rows then, from the eta this kernel left behind.
 __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, int64_t n,
                                                    int64_t ld, const int32_t* __restrict__ slots,
                                                    float* __restrict__ eta,
@@ -168,7 +170,7 @@ __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, 
     const float* dv = deta ? deta + (int64_t)k * ld : nullptr;
     const float* yv = Y + (int64_t)fit_resp[k] * ld;
     const uint8_t* m = M + (int64_t)fit_mask[k] * ld;
-    float* w = W + (int64_t)k * ld;
+    float* w = W ? W + (int64_t)k * ld : nullptr;
     float* r = R ? R + (int64_t)k * ld : nullptr;
     const int64_t plane = (int64_t)Bp * ld;
     __bf16* rp = (Rp && ry >= 0) ? Rp + (int64_t)ry * ld : nullptr;
@@ -188,7 +190,7 @@ __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, 
                 ri = mi * o.g;
             }
         }
-        w[i] = wi;
+        if (w) w[i] = wi;
         if (r) r[i] = ri;
         if (rp) {
             __bf16 hi, mid, lo;
@@ -197,6 +199,33 @@ __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, 
             rp[plane + i] = mid;
             rp[2 * plane + i] = lo;
         }
+    }
+}
+
+// W[k][i] of link_kernel alone (k = slots[y], all slots when slots is null), from the same
+// expression on the same eta: bitwise the weights that kernel writes.
+__global__ void __launch_bounds__(256) link_weights_kernel(
+    int32_t family, float power, int64_t n, int64_t ld, const int32_t* __restrict__ slots,
+    const float* __restrict__ eta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
+    const int32_t* __restrict__ fit_resp, const int32_t* __restrict__ fit_mask,
+    float* __restrict__ W) {
+    const int y = blockIdx.y;
+    const int k = slots ? slots[y] : y;
+    const float* e = eta + (int64_t)k * ld;
+    const float* yv = Y + (int64_t)fit_resp[k] * ld;
+    const uint8_t* m = M + (int64_t)fit_mask[k] * ld;
+    float* w = W + (int64_t)k * ld;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ld;
+         i += (int64_t)gridDim.x * 256) {
+        float wi = 0.0f;
+        if (i < n) {
+            const float mi = (float)m[i];
+            if (mi != 0.0f) {
+                const LossOut o = half_loss(family, power, yv[i], e[i]);
+                wi = mi * o.h;
+            }
+        }
+        w[i] = wi;
     }
 }
 
@@ -319,21 +348,26 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
     float mx = 0.0f;
     const int64_t i0 = (int64_t)blockIdx.x * kRowChunk;
     const int64_t i1 = min(i0 + kRowChunk, n);
-    // Poisson with the first-round step lengths {0, 1, 1/2, 1/4, 1/8}: exp(eta + t d) =
-    // exp(eta) exp(d/8)^(8t) -- two exps and three squarings per row instead of five exps
+    // Poisson with the first-round step lengths {0, 1, 1/2, 1/4, 1/8}: the line search reads
+    // only L(t) - L(0), so the trials are summed as differences,
+    //   l(t) - l(0) = mu (exp(t d) - 1) - y t d,   mu = exp(eta),
+    // with x(t) = exp(t d) - 1 from one expm1f(d/8) and three squarings x(2t) = x(t)(2 + x(t))
+    // (no cancellation): two f32 transcendentals per row, the terms and sums in float64.
+    // acc[0] holds L(0), acc[j >= 1] the difference; the block's partial of trial j is their sum.
     const bool halving = family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f && T == 5 &&
                          tv[0] == 0.0f && tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f &&
                          tv[4] == 0.125f;
     if (halving) {
-        auto row = [&](double mi, double yi, double ei, double di) {
-            mx = fmaxf(mx, fabsf((float)di));
-            const double mu = exp(ei), e8 = exp(0.125 * di);
-            const double e4 = e8 * e8, e2 = e4 * e4, e1 = e2 * e2;
-            acc[0] += mi * (mu - yi * ei);
-            acc[1] += mi * (mu * e1 - yi * (ei + di));
-            acc[2] += mi * (mu * e2 - yi * (ei + 0.5 * di));
-            acc[3] += mi * (mu * e4 - yi * (ei + 0.25 * di));
-            acc[4] += mi * (mu * e8 - yi * (ei + 0.125 * di));
+        auto row = [&](double mi, float yi, float ei, float di) {
+            mx = fmaxf(mx, fabsf(di));
+            const float muf = expf(ei), x8 = expm1f(0.125f * di);
+            const float x4 = x8 * (2.0f + x8), x2 = x4 * (2.0f + x4), x1 = x2 * (2.0f + x2);
+            const double mu = muf, yd = (double)yi * (double)di;
+            acc[0] += mi * (mu - (double)yi * (double)ei);
+            acc[1] += mi * (mu * (double)x1 - yd);
+            acc[2] += mi * (mu * (double)x2 - 0.5 * yd);
+            acc[3] += mi * (mu * (double)x4 - 0.25 * yd);
+            acc[4] += mi * (mu * (double)x8 - 0.125 * yd);
         };
         // four consecutive rows per thread from 4-byte / 16-byte loads (rows are 16-byte
         // aligned: ld and the chunk starts are multiples of 256): four times the bytes in
@@ -367,11 +401,14 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
                 acc[j] += mi * half_loss_d(family, (double)power, yi, ei + (double)tv[j] * di);
         }
     }
+    double s0 = 0.0;
     for (int j = 0; j < T; ++j) {
-        const double s = block_sum_d(acc[j], sh);
+        double s = block_sum_d(acc[j], sh);
+        if (j == 0) s0 = s;
+        else if (halving) s += s0;
         if (threadIdx.x == 0) part[((int64_t)q * T + j) * nchunks + blockIdx.x] = s;
     }
-    if (dmax) {                 // max |d_eta| over the fit's rows (Hessian drift bound)
+    if (dmax) {                // max |d_eta| over the fit's rows (Hessian drift bound)
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
         if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = mx;
         __syncthreads();
@@ -402,9 +439,11 @@ __global__ void __launch_bounds__(256) score_kernel(
         const double w1 = m1 ? (double)m1[i] : 0.0;
         if (w0 == 0.0 && w1 == 0.0) continue;
         const double yi = y[i], ei = e[i];
+        // Poisson: mu = exp(eta) is also the loss's exponential, evaluated once
+        const bool pois = family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f;
         const double mu = inv_link_d(family, ei);
         const double r2 = (yi - mu) * (yi - mu);
-        const double l = half_loss_d(family, (double)power, yi, ei);
+        const double l = pois ? mu - yi * ei : half_loss_d(family, (double)power, yi, ei);
         acc[0] += w0 * r2; acc[1] += w0 * l;
         acc[2] += w1 * r2; acc[3] += w1 * l;
     }
@@ -414,14 +453,24 @@ __global__ void __launch_bounds__(256) score_kernel(
     }
 }
 
+// One wave per output row (four rows per block): lane l sums chunks l, l + 64, ... in ascending
+// order (coalesced loads), then the fixed butterfly of wave_sum_d -- one order whatever the
+// scheduling.  reduce_grid(): the launch geometry.
+constexpr int kReduceRows = 4;
+static dim3 reduce_grid(int64_t rows) {
+    return dim3((unsigned)((rows + kReduceRows - 1) / kReduceRows));
+}
 __global__ void __launch_bounds__(256) reduce_chunks_d(const double* __restrict__ part,
                                                        int64_t rows, int32_t nchunks,
                                                        double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * kReduceRows + (threadIdx.x >> 6);
+    if (e >= rows) return;                       // wave-uniform
+    const double* p = part + e * nchunks;
     double s = 0.0;
-    for (int c = 0; c < nchunks; ++c) s += part[e * nchunks + c];
-    out[e] = s;
+    for (int c = lane; c < nchunks; c += 64) s += p[c];
+    s = wave_sum_d(s);
+    if (lane == 0) out[e] = s;
 }
 
 __global__ void __launch_bounds__(256) eta_axpy_kernel(int64_t n, int64_t ld,
@@ -471,38 +520,73 @@ __global__ void __launch_bounds__(256) eta_axpy_max_kernel(int64_t n, int64_t ld
 // out[q] = max over the rows of mask fit_mask[a] of |eta[a][i] - eta[b][i]|, (a, b) =
 // pairs[2q], pairs[2q+1] (same mask): how far apart the IRLS weights of two fits are, which
 // decides whether b may be factored from a's Gram.  out must be zeroed.
+//
+// A workgroup takes kPairGroup consecutive pairs over its rows.  The engine lists pairs that
+// share a fit next to each other (a lambda chain (c0,c1), (c1,c2), ...; the candidates of one
+// representative), so a fit's four rows that the previous pair of the group already loaded are
+// taken from registers: the fit ids are wave-uniform, and a lane keeps a flag for whether it
+// loaded (it skips the loads where its four mask bytes are all zero).
+constexpr int kPairGroup = 4;
 __global__ void __launch_bounds__(256) eta_pair_absmax_kernel(
-    int64_t n, int64_t ld, const int32_t* __restrict__ pairs, const uint8_t* __restrict__ M,
-    const int32_t* __restrict__ fit_mask, const float* __restrict__ eta, float* __restrict__ out) {
-    const int q = blockIdx.y;
-    const int a = pairs[2 * q], b = pairs[2 * q + 1];
-    const float* ea = eta + (int64_t)a * ld;
-    const float* eb = eta + (int64_t)b * ld;
-    const uint8_t* m = M + (int64_t)fit_mask[a] * ld;
-    float mx = 0.0f;
+    int64_t n, int64_t ld, int32_t npairs, const int32_t* __restrict__ pairs,
+    const uint8_t* __restrict__ M, const int32_t* __restrict__ fit_mask,
+    const float* __restrict__ eta, float* __restrict__ out) {
+    const int q0 = blockIdx.y * kPairGroup;
+    const int ng = min(kPairGroup, npairs - q0);
+    float mx[kPairGroup];
+#pragma unroll
+    for (int g = 0; g < kPairGroup; ++g) mx[g] = 0.0f;
     // four consecutive rows per thread (4-byte mask / 16-byte eta loads; rows 16-byte aligned)
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n;
          i += (int64_t)gridDim.x * 1024) {
         if (i + 4 <= n) {
-            const uint32_t m4 = *reinterpret_cast<const uint32_t*>(m + i);
-            if (m4 == 0u) continue;
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(ea + i);
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(eb + i);
+            int ha = -1, hb = -1;               // fits held in ra / rb (wave-uniform)
+            bool oka = false, okb = false;      // ... and whether this lane loaded them
+            f32x4 ra = {}, rb = {};
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if ((m4 >> (8 * j)) & 0xffu) mx = fmaxf(mx, fabsf(a4[j] - b4[j]));
+            for (int g = 0; g < kPairGroup; ++g) {
+                if (g >= ng) break;
+                const int a = pairs[2 * (q0 + g)], b = pairs[2 * (q0 + g) + 1];
+                const uint32_t m4 =
+                    *reinterpret_cast<const uint32_t*>(M + (int64_t)fit_mask[a] * ld + i);
+                const bool act = m4 != 0u;
+                f32x4 na = {}, nb = {};
+                if (act) {
+                    if (a == ha && oka) na = ra;
+                    else if (a == hb && okb) na = rb;
+                    else na = *reinterpret_cast<const f32x4*>(eta + (int64_t)a * ld + i);
+                    if (b == hb && okb) nb = rb;
+                    else if (b == ha && oka) nb = ra;
+                    else nb = *reinterpret_cast<const f32x4*>(eta + (int64_t)b * ld + i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if ((m4 >> (8 * j)) & 0xffu) mx[g] = fmaxf(mx[g], fabsf(na[j] - nb[j]));
+                }
+                ra = na; rb = nb; oka = okb = act; ha = a; hb = b;
+            }
         } else {
-            for (int64_t q2 = i; q2 < n; ++q2)
-                if (m[q2]) mx = fmaxf(mx, fabsf(ea[q2] - eb[q2]));
+            for (int g = 0; g < ng; ++g) {
+                const int a = pairs[2 * (q0 + g)], b = pairs[2 * (q0 + g) + 1];
+                const uint8_t* m = M + (int64_t)fit_mask[a] * ld;
+                const float* ea = eta + (int64_t)a * ld;
+                const float* eb = eta + (int64_t)b * ld;
+                for (int64_t q2 = i; q2 < n; ++q2)
+                    if (m[q2]) mx[g] = fmaxf(mx[g], fabsf(ea[q2] - eb[q2]));
+            }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    __shared__ float sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
+    __shared__ float sh[kPairGroup][4];
+#pragma unroll
+    for (int g = 0; g < kPairGroup; ++g) {
+        float v = mx[g];
+        for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+        if ((threadIdx.x & 63) == 0) sh[g][threadIdx.x >> 6] = v;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-        atomicMax(reinterpret_cast<unsigned int*>(out + q), __float_as_uint(mx));
+    if ((int)threadIdx.x < ng) {
+        const float* s = sh[threadIdx.x];
+        atomicMax(reinterpret_cast<unsigned int*>(out + q0 + threadIdx.x),
+                  __float_as_uint(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]))));
     }
 }
 
@@ -559,15 +643,20 @@ __global__ void __launch_bounds__(256) mask_stats_kernel(const uint8_t* __restri
 __global__ void __launch_bounds__(256) mask_stats_reduce(const double* __restrict__ part,
                                                          int64_t rows, int32_t nch,
                                                          double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= rows) return;
+    // one wave per output row, as reduce_chunks_d (the fifth statistic is a minimum)
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * kReduceRows + (threadIdx.x >> 6);
+    if (e >= rows) return;                       // wave-uniform
     const bool is_min = e % kStat == kStat - 1;
+    const double* p = part + e * nch;
     double s = is_min ? INFINITY : 0.0;
-    for (int c = 0; c < nch; ++c) {
-        const double v = part[e * nch + c];
-        s = is_min ? fmin(s, v) : s + v;
+    for (int c = lane; c < nch; c += 64) s = is_min ? fmin(s, p[c]) : s + p[c];
+    if (is_min) {
+        for (int o = 32; o > 0; o >>= 1) s = fmin(s, __shfl_xor(s, o, 64));
+    } else {
+        s = wave_sum_d(s);
     }
-    out[e] = s;
+    if (lane == 0) out[e] = s;
 }
 
 // Per-fit scalars of a Newton step, one workgroup per active fit k = slots[q] (float64): the
@@ -957,7 +1046,7 @@ int sglm_link_update(int32_t family, float power, int64_t n, int64_t ld, int32_t
                      const int32_t* fit_resp, const int32_t* fit_mask, float* W, float* R,
                      void* Rp, const float* step, const float* deta, sglm_stream_t stream) {
     if (B <= 0) return SGLM_OK;
-    if (!eta || !Y || !M || !fit_resp || !fit_mask || !W || (!R && !Rp)) { set_error("sglm_link_update: null pointer"); return SGLM_EINVAL; }
+    if (!eta || !Y || !M || !fit_resp || !fit_mask || (!R && !Rp)) { set_error("sglm_link_update: null pointer"); return SGLM_EINVAL; }
     dim3 grid(grid1(ld, 256, 1024), (unsigned)B);
     link_kernel<<<grid, 256, 0, as_stream(stream)>>>(family, power, n, ld, slots, eta, Y, M,
                                                      fit_resp, fit_mask, W, R, (__bf16*)Rp,
@@ -971,7 +1060,7 @@ int sglm_link_update_rp(int32_t family, float power, int64_t n, int64_t ld, int3
                         void* Rp, int32_t Bp, const int32_t* rpos, const float* step,
                         const float* deta, sglm_stream_t stream) {
     if (B <= 0) return SGLM_OK;
-    if (!eta || !Y || !M || !fit_resp || !fit_mask || !W || (!R && !Rp) || !slots ||
+    if (!eta || !Y || !M || !fit_resp || !fit_mask || (!R && !Rp) || !slots ||
         (Rp && (!rpos || Bp < B || Bp % 32)) || (deta && !step)) {
         set_error("sglm_link_update_rp: bad args");
         return SGLM_EINVAL;
@@ -981,6 +1070,21 @@ int sglm_link_update_rp(int32_t family, float power, int64_t n, int64_t ld, int3
                                                      fit_resp, fit_mask, W, R, (__bf16*)Rp, Bp,
                                                      step, deta, rpos);
     return check_launch("link_kernel");
+}
+
+int sglm_link_weights(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
+                      const int32_t* slots, const float* eta, const float* Y, const uint8_t* M,
+                      const int32_t* fit_resp, const int32_t* fit_mask, float* W,
+                      sglm_stream_t stream) {
+    if (B <= 0) return SGLM_OK;
+    if (!eta || !Y || !M || !fit_resp || !fit_mask || !W || n > ld) {
+        set_error("sglm_link_weights: bad args");
+        return SGLM_EINVAL;
+    }
+    dim3 grid(grid1(ld, 256, 1024), (unsigned)B);
+    link_weights_kernel<<<grid, 256, 0, as_stream(stream)>>>(family, power, n, ld, slots, eta, Y,
+                                                             M, fit_resp, fit_mask, W);
+    return check_launch("link_weights_kernel");
 }
 
 size_t sglm_xtr_work_bytes(int32_t P, int32_t B, int64_t n) {
@@ -1027,7 +1131,7 @@ int sglm_loss_trials(int32_t family, float power, int64_t n, int64_t ld, int32_t
     int st = check_launch("loss_trials_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
-    reduce_chunks_d<<<grid1(rows, 256), 256, 0, s>>>((const double*)work, rows, nc, out);
+    reduce_chunks_d<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);
     return check_launch("reduce_chunks_d");
 }
 
@@ -1050,7 +1154,7 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
     int st = check_launch("loss_trials_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
-    reduce_chunks_d<<<grid1(rows, 256), 256, 0, s>>>((const double*)work, rows, nc, out);
+    reduce_chunks_d<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);
     return check_launch("reduce_chunks_d");
 }
 
@@ -1094,8 +1198,8 @@ int sglm_eta_pair_absmax(int64_t n, int64_t ld, int32_t npairs, const int32_t* p
         set_error("sglm_eta_pair_absmax: hipMemsetAsync failed");
         return SGLM_EHIP;
     }
-    dim3 grid(grid1(n, 256, 256), (unsigned)npairs);
-    eta_pair_absmax_kernel<<<grid, 256, 0, s>>>(n, ld, pairs, M, fit_mask, eta, out);
+    dim3 grid(grid1(n, 256, 256), (unsigned)((npairs + kPairGroup - 1) / kPairGroup));
+    eta_pair_absmax_kernel<<<grid, 256, 0, s>>>(n, ld, npairs, pairs, M, fit_mask, eta, out);
     return check_launch("eta_pair_absmax_kernel");
 }
 
@@ -1176,7 +1280,7 @@ int sglm_mask_stats(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, i
     int st = check_launch("mask_stats_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)R * F * kStat;
-    mask_stats_reduce<<<grid1(rows, 256), 256, 0, s>>>((const double*)work, rows, nc, out);
+    mask_stats_reduce<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);
     return check_launch("mask_stats_reduce");
 }
 
@@ -1192,7 +1296,7 @@ int sglm_score_sums(int32_t family, float power, int64_t n, int64_t ld, int32_t 
     int st = check_launch("score_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * 4;
-    reduce_chunks_d<<<grid1(rows, 256), 256, 0, s>>>((const double*)work, rows, nc, out);
+    reduce_chunks_d<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);
     return check_launch("reduce_chunks_d");
 }
 

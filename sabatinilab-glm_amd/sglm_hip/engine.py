@@ -1806,6 +1806,9 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 if int(k) in store:
                     comm.sum_(store[int(k)])
     bf.prob, bf.fit_mask, bf.fit_mask_d = prob, fmask_h, fit_mask
+    # the links below store no W: a Gram's weights are written when it is formed, from the
+    # predictor the last link left behind (_link_weights)
+    bf.wlink = (fam, power, n, ld, prob.Y, prob.M, fit_resp, fit_mask)
     bf.mixS = {}
     # cross-mask families (slot of the representative per slot, -1: none / is one)
     xmask_tol = 0.0 if const_hess else HESS_XMASK_TOL / max(1.0, abs(2.0 - power))
@@ -1863,9 +1866,8 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 k_h.append(int(k))
             fkey[k] = keys[key]
         k_h = np.asarray(k_h, dtype=np.int32)
-        # the exact mask Gram of each (W = the mask's multiplicities; the fit's first link update
-        # overwrites W -- a fit whose first link GRAD_DEDUP skips keeps them, which is why such
-        # a fit is never the Gram representative of its start key, see the lead choice there)
+        # the exact mask Gram of each (W = the mask's multiplicities, set here; every later Gram
+        # of the fit has its weights written by _link_weights first)
         kh_d = up(k_h, np.int64)
         bf.W[kh_d] = prob.M[up(fmask_h[k_h], np.int64)].float()
         _syrk(d, bf, k_h, nsteps, ntile1, None, st, exact=True, rows=gram_rows)
@@ -1914,7 +1916,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             chains = [sorted(g, key=lambda k: lam[k]) for g in groups.values() if len(g) > 1]
         pairs = [(int(k), int(repl[k])) for k in cand]
         pairs += [(c[i], c[i + 1]) for c in chains for i in range(len(c) - 1)]
-        ev = None
+        ev, porder = None, None
         if pairs and len(pairs) > pd_h.numel():
             raise RuntimeError("pair distance buffer too small")
         if pairs and not warm and all(fresh_start[a] and fresh_start[b]
@@ -1926,14 +1928,15 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             pd_h[:len(pairs)].copy_(torch.from_numpy(np.abs(ic32[pa[:, 0]] - ic32[pa[:, 1]])))
         elif pairs:
             npair = len(pairs)
-            pd_d = _pair_dist_async(bf, prob, np.array(pairs, dtype=np.int32), n, ld, st)
+            pd_d, porder = _pair_dist_async(bf, prob, np.array(pairs, dtype=np.int32), n, ld, st,
+                                            ncand=int(cand.size))
             if comm is not None:
                 comm.max_(pd_d)
             pd_h[:npair].copy_(pd_d, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         return dict(cand=cand, keep=keep, form=form, reps=reps, dup=dup, uniq=uniq,
-                    chains=chains, npairs=len(pairs), ev=ev)
+                    chains=chains, npairs=len(pairs), ev=ev, porder=porder)
 
     def hess_finish(pl):
         """Apply the distances of a plan: lambda-neighbour sharing, then aliasing of the
@@ -1947,6 +1950,10 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         if pl["ev"] is not None:
             pl["ev"].synchronize()
         dist = pd_h[:pl["npairs"]].numpy().astype(np.float64)
+        if pl["porder"] is not None:
+            # the launch listed the candidates by representative: back to the plan's order
+            launched, dist = dist, np.empty_like(dist)
+            dist[pl["porder"]] = launched
         cand, keep, form, reps, dup, uniq = (pl[k] for k in ("cand", "keep", "form", "reps",
                                                              "dup", "uniq"))
         dist_c, dist_s = dist[:cand.size], dist[cand.size:]
@@ -2024,12 +2031,11 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             # (hkey) have one predictor, hence bitwise one W, R and X^T R: the link and the
             # gradient run once per key and the other fits' gradient rows are copies (at C4:
             # 6 of 120 fits in the first iteration, where the factorisation chain runs beside
-            # the gradient).  A copied fit's R is not read before its next link, but its W is the
-            # Gram operand if hess_plan makes it the representative of its key -- the first fit
-            # of the key that is no cross-mask candidate, e.g. an unpenalised fit listed after
-            # penalised ones, whose W still holds the mask multiplicities of the rank Gram above
-            # -- so the lead is chosen by that rule: the first fit of the key that forms its
-            # own Hessian, else (all candidates: a failed one forms in this order) the first
+            # the gradient).  A copied fit's R is not read before its next link, and the Gram
+            # weights of whichever fit hess_plan makes the representative of its key are written
+            # from that fit's own predictor (_link_weights).  The lead is the first fit of the
+            # key that forms its own Hessian, else (all candidates: a failed one forms in this
+            # order) the first
             own_ok = drift[act] <= reuse_tol
             is_cand = (repl[act] >= 0) & ~no_alias[act] & ~own_ok
             lead_of, first = {}, {}
@@ -2053,11 +2059,11 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         if fused and not dev_linked:
             if linked is None:
                 _lib.call("sglm_link_update", fam, power, n, ld, link_n, _p(link_d), _p(bf.eta),
-                          _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), _p(bf.W), R_out,
+                          _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), None, R_out,
                           Rp_out, None, None, st)
         else:
             _lib.call("sglm_link_update", fam, power, n, ld, B, None, _p(bf.eta), _p(prob.Y),
-                      _p(prob.M), _p(fit_resp), _p(fit_mask), _p(bf.W), _p(bf.R), None, None,
+                      _p(prob.M), _p(fit_resp), _p(fit_mask), None, _p(bf.R), None, None,
                       None, st)
 
         grad_done = [False]
@@ -2111,6 +2117,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 for k in act:
                     reps.setdefault(reqs[k].mask, k)
                 rep_idx = np.array(sorted(reps.values()), dtype=np.int32)
+                _link_weights(bf, rep_idx, st)      # squared loss: the masks' multiplicities
                 _syrk(d, bf, rep_idx, nsteps, ntile1, stats, st, exact=True, rows=gram_rows)
                 sum_hess(rep_idx)
                 gram_comp[rep_idx] = True
@@ -2435,7 +2442,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             _lib.call("sglm_step_update", P, na, _p(act_d), _p(dec64[0]), _p(bf.delta),
                       _p(beta64_d), st)
             _lib.call("sglm_link_update_rp", fam, power, n, ld, na, _p(act_d), _p(bf.eta),
-                      _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), _p(bf.W), None,
+                      _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), None, None,
                       _p(rp_buf), pad_to(na, 32), _p(deci[2 * B0:]), _p(dec32), _p(bf.deta), st)
         t_sync = time.perf_counter()
         if dev_dec:
@@ -2574,7 +2581,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                     if mc.size:
                         _lib.call("sglm_link_update_rp", fam, power, n, ld, int(mc.size),
                                   _p(mc_d), _p(bf.eta), _p(prob.Y), _p(prob.M), _p(fit_resp),
-                                  _p(fit_mask), _p(bf.W), None, _p(rp_buf), pad_to(na, 32),
+                                  _p(fit_mask), None, None, _p(rp_buf), pad_to(na, 32),
                                   _p(mr_d), None, None, st)
             up.flush()
             grad_d, grad_n, grad_bp = deci[3 * B0:], int(di[4 * B0]), pad_to(na, 32)
@@ -2592,7 +2599,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 _lib.call("sglm_eta_axpy", n, ld, int(done.size), _p(done_d), _p(tdone_d),
                           _p(bf.deta), _p(bf.eta), st)
             _lib.call("sglm_link_update", fam, power, n, ld, int(nxt.size), _p(linked),
-                      _p(bf.eta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), _p(bf.W),
+                      _p(bf.eta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), None,
                       R_out, Rp_out, _p(tcont_d), _p(bf.deta), st)
         else:
             t32_d = up(step_a, np.float32)
@@ -2700,7 +2707,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         cnt = outs[B0 * P + B0:].astype(np.int64)
         has = fkey >= 0
         out_info[has] = np.maximum(0 if const_hess else out_info[has], cnt[fkey[has]])
-    bf.prob = bf.keep = bf.up = bf.fit_mask_d = None   # drop the compacted designs with the problem
+    bf.prob = bf.keep = bf.up = bf.fit_mask_d = bf.wlink = None   # drop the compacted designs with the problem
     bf.mixS = None
     res = []
     for k, r in enumerate(reqs0):
@@ -2994,12 +3001,24 @@ def irls_scored(prob: Problem, reqs: List[FitReq], sets: np.ndarray,
     return res, sums
 
 
-def _pair_dist_async(bf, prob, pairs, n, ld, st):
+def _pair_dist_async(bf, prob, pairs, n, ld, st, ncand=0):
     """Device float32 [len(pairs)]: max over the rows of fit a's mask of |eta_a - eta_b| for
-    each (a, b) in pairs (enqueued, not waited for)."""
+    each (a, b) in pairs (enqueued, not waited for), and the launch order.
+
+    The kernel reads a fit that two neighbouring pairs share once, so the first ``ncand`` pairs
+    (candidate, representative) are launched sorted stably by representative; the lambda chains
+    behind them already list neighbours next to each other.  Returns (out, order): out[j] is
+    the distance of pairs[order[j]] (order None: the caller's own order)."""
     dev = bf.eta.device
     upl = getattr(bf, "up", None)
-    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    order = None
+    if ncand > 1:
+        co = np.argsort(pairs[:ncand, 1], kind="stable")
+        if not np.array_equal(co, np.arange(ncand)):
+            order = np.concatenate([co, np.arange(ncand, pairs.shape[0])])
+            pairs = pairs[order]
+    pairs = np.ascontiguousarray(pairs).reshape(-1)
     pd_ = upl(pairs) if upl is not None else torch.from_numpy(pairs).to(dev)
     fm = getattr(bf, "fit_mask_d", None)
     if fm is None:
@@ -3007,7 +3026,7 @@ def _pair_dist_async(bf, prob, pairs, n, ld, st):
     out = torch.empty(pairs.size // 2, dtype=torch.float32, device=dev)
     _lib.call("sglm_eta_pair_absmax", n, ld, pairs.size // 2, _p(pd_), _p(prob.M), _p(fm),
               _p(bf.eta), _p(out), st)
-    return out
+    return out, order
 
 
 def _resolve_copies(src, formed):
@@ -3057,6 +3076,7 @@ def _lag_gram(d: Design, bf, fits: np.ndarray, st):
     """H[k] = w_k X^T X for fits at a constant weight over every row (sglm_lag_gram: event
     cross-correlations instead of the MFMA Gram)."""
     lg = d.lag
+    _link_weights(bf, fits, st)
     work = _work(_lib.query("sglm_lag_gram_work_bytes", lg.m, lg.smin, lg.smax), d.device,
                  "laggram")
     upl = getattr(bf, "up", None)
@@ -3141,6 +3161,22 @@ class _Factor64:
                   _p(work), st)
 
 
+def _link_weights(bf, fits, st):
+    """W[fits] = the IRLS weights m * loss''(eta) at the fits' current predictors
+    (sglm_link_weights), on the stream of the Gram that reads them.  irls links without storing
+    W (bf.wlink holds its link arguments): these are bitwise the rows the last link would have
+    written.  Outside an irls solve (no bf.wlink) W is the caller's."""
+    lw = getattr(bf, "wlink", None)
+    fits = np.ascontiguousarray(fits, dtype=np.int32).reshape(-1)
+    if lw is None or fits.size == 0:
+        return
+    fam, power, n, ld, Y, M, fit_resp, fit_mask = lw
+    upl = getattr(bf, "up", None)
+    fits_d = upl(fits, np.int32) if upl is not None else torch.from_numpy(fits).to(bf.W.device)
+    _lib.call("sglm_link_weights", fam, power, n, ld, int(fits.size), _p(fits_d), _p(bf.eta),
+              _p(Y), _p(M), _p(fit_resp), _p(fit_mask), _p(bf.W), st)
+
+
 def _syrk(d: Design, bf, fits: np.ndarray, nsteps: int, ntile1: int, stats, st, exact=False,
           rows=None):
     """H[k] = X^T diag(W[k]) X for k in fits.  bf16 MFMA, or the exact-f32 MFMA variant when
@@ -3148,6 +3184,8 @@ def _syrk(d: Design, bf, fits: np.ndarray, nsteps: int, ntile1: int, stats, st, 
     nact = int(fits.size)
     if nact == 0:
         return
+    if not exact:
+        _link_weights(bf, fits, st)
     use_f32 = exact and d.xf is not None
     prob = getattr(bf, "prob", None)
     use_cb = not use_f32 and d.xbits is not None and SYRK_CBITS and prob is not None
