@@ -471,6 +471,40 @@ int sglm_chol64_minnorm(const double* U, int32_t P, int32_t pw, const uint8_t* s
                         const int32_t* fits, const int32_t* fsrc, int32_t nfit, double* beta,
                         void* work, sglm_stream_t stream);
 
+/* --- reduced (column-deleted) squared-loss solves off the full model's float64 factor -----
+ * The reference's production drivers loop over leave_one_out_list: the full model, then one
+ * whole run (timeshift, folds, CV grid, refit, holdout score) per left-out event with that
+ * event's columns deleted from X.  The reduced normal equations are a principal submatrix of
+ * the full model's, so these two calls replace the per-event refactorisation.  With
+ * A = G + diag(lam') = U^T U (sglm_chol64_factor), a drop set S (k sorted coordinates),
+ * W = U^-T E_S and T = W^T W = (A^-1)_SS, the reduced solution is x = U^-1 (z - W T^-1 W^T z)
+ * for z = U^-T c: 0 on S, solve(A[keep, keep], c[keep]) elsewhere.
+ * Drop sets: sets (int32 [ng][kmax], padded) and lens (int32 [ng]); kmax <=
+ * sglm_chol64_drop_kmax() (64).  Pairs p < npair: factor pf[p], set pg[p].
+ * sglm_chol64_drop_prep: per pair, W [P][kmax] (float64) and the upper Cholesky factor of T
+ *   ([64][64]) into work, and status[p]: 0 ok, 1 a pivot of T is not positive, 2 the factor has
+ *   dependent or zero coordinates (counts[2 f + 1] != 0) or the set is longer than kmax -- the
+ *   caller then excludes the coordinates through dshift instead.  Coordinates of S that are not
+ *   kept in the factor (state != 0) are treated as already absent.
+ *   work: sglm_chol64_drop_work_bytes(P, npair, kmax).  P % 64 == 0, P <= 8192.
+ * sglm_chol64_drop_solve_add: x[fits[q]] += the reduced solve of g[gsrc[q]] (gsrc NULL: the
+ *   fit's own row) on factor fsrc[q] with pair psrc[q]; exact 0.0 is stored on the pair's set,
+ *   nothing is added on coordinates the factor does not keep.  A pair whose status is not 0 is
+ *   skipped (x untouched).  work / status as prep left them (same npair, kmax).  Async on
+ *   stream, no allocation, fixed reduction orders (bitwise repeatable). */
+int32_t sglm_chol64_drop_kmax(void);
+size_t sglm_chol64_drop_work_bytes(int32_t P, int32_t npair, int32_t kmax);
+int sglm_chol64_drop_prep(const double* U, int32_t P, const uint8_t* state, const int32_t* counts,
+                          const int32_t* pf, const int32_t* pg, int32_t npair,
+                          const int32_t* sets, const int32_t* lens, int32_t kmax, void* work,
+                          int32_t* status, sglm_stream_t stream);
+int sglm_chol64_drop_solve_add(const double* U, int32_t P, const uint8_t* state,
+                               const int32_t* fits, const int32_t* fsrc, const int32_t* gsrc,
+                               const int32_t* psrc, int32_t nq, const double* g, double* x,
+                               const int32_t* pg, int32_t npair, const int32_t* sets,
+                               const int32_t* lens, int32_t kmax, const void* work,
+                               const int32_t* status, sglm_stream_t stream);
+
 /* Per-fit scalars of a Newton step for the B fits k = slots[q], float64 (one workgroup per
  * fit): out[q][0..6+T) = { g.d, sum lam w^2, sum lam w d, sum lam d^2, max|d_a|,
  * max|w_a + t[j] d_a| for j < T, max|d_b| } over the P coordinates of g[k] (float64), beta[k]

@@ -151,6 +151,118 @@ def simple_cv_fit(X, y, cv_idx, glm_kwarg_lst, model_type='Normal', verbose=0, s
             cv_results['best_model'], cv_results)
 
 
+def left_out_columns(X, left_out):
+    """Positions (ascending) of the columns of frame ``X`` that leaving out the base names
+    ``left_out`` removes: each name's own column and all its shifted columns -- by the lagged
+    frame's own column-to-source map while it is lazy, else by ``add_timeshifts_to_col_list``'s
+    naming (``f"{name}_{shift}"``).  A name that matches no column raises KeyError."""
+    import re
+    cols = list(X.columns)
+    spec = X._spec if isinstance(X, LagFrame) and X.is_lazy else None
+    out = set()
+    for name in left_out:
+        if spec is not None:
+            hit = [i for i, c in enumerate(cols)
+                   if (c not in X._overlay and spec[c][0] == name) or c == name]
+        else:
+            pat = re.compile(re.escape(str(name)) + r"(_-?\d+)?$")
+            hit = [i for i, c in enumerate(cols) if pat.match(str(c))]
+        if not hit:
+            raise KeyError(name)
+        out.update(hit)
+    return sorted(out)
+
+
+def reduce_cv_result(r, drop, glm_kwargs, model_name):
+    """One parameter's grid result dict (full length p, zeros on the dropped columns ``drop``)
+    as the reference's loop over column-deleted frames reports it: coefficients of the kept
+    columns only, in the frame's column order, and the refit installed in a fresh GLM."""
+    p = r["cv_coefs"].shape[0]
+    keep = np.setdiff1d(np.arange(p), np.asarray(drop, dtype=np.int64))
+    glm = sglm_.GLM(model_name, **glm_kwargs)
+    glm._set_fitted(np.asarray(r["refit_coef"])[keep], r["refit_intercept"], max(r["n_iter"]))
+    d = {k: r[k] for k in ("cv_coefs", "cv_intercepts", "cv_scores_train", "cv_scores_test",
+                           "cv_mean_score_train", "cv_mean_score", "cv_std_score",
+                           "cv_R2_score", "cv_mse_score")}
+    d["cv_coefs"] = r["cv_coefs"][keep]
+    d["glm_kwargs"] = glm_kwargs
+    d["model"] = glm
+    if "refit_holdout_r2" in r:
+        d["holdout_score"] = r["refit_holdout_r2"]
+        d["holdout_neg_mse_score"] = r["refit_holdout_neg_mse"]
+    return d
+
+
+def leave_one_out_cv_fit(X, y, cv_idx, glm_kwarg_lst, left_out_list, model_type='Normal',
+                         verbose=0, score_method='mse', X_holdout=None, y_holdout=None):
+    """The production drivers' ``for left_out in leave_one_out_list`` loop around
+    ``simple_cv_fit`` (er_refactored_from_scratch_ignoreSideInInfo.py:321-330, 475-546) as ONE
+    batched solve on one resident design: every entry of ``left_out_list`` (a list of base
+    column names, ``[]`` = the full model) removes those columns and all their shifted columns.
+
+    Returns ``{tuple(left_out): (best_score, best_score_std, best_params, best_model,
+    cv_results)}`` -- per entry what ``simple_cv_fit`` on the column-deleted frame returns
+    (coefficients of the reduced length, in the reduced frame's column order; first strict
+    maximum over the parameter list, sglm_cv.py:402-415).  With holdout data each tuple also
+    ends with the best refit's ``holdout_score`` (R^2) and ``holdout_neg_mse_score``
+    (``training_fit_holdout_score``).  ``X_holdout``: a frame with X's columns (``y_holdout``
+    its response), or a 1-D array of row indices of ``X`` -- the holdout rows then ride the same
+    design, the other rows are the setup rows, and ``cv_idx`` indexes the setup rows."""
+    from sglm_hip import grid as _grid
+    left_out_list = [list(lo) for lo in left_out_list]
+    drops = [left_out_columns(X, lo) for lo in left_out_list]
+    params = []
+    for glm_kwargs in glm_kwarg_lst:
+        glm_kwargs = dict(glm_kwargs)
+        mn = glm_kwargs.pop('model_name', 'Gaussian')
+        roll = glm_kwargs.pop('roll', 0)
+        params.append((mn, glm_kwargs, roll))
+    objectives = [sglm_.GLM(mn, **kw, score_method=score_method).model.objective()
+                  for mn, kw, _ in params]
+    yv = np.asarray(y.values if hasattr(y, "values") and not isinstance(y, np.ndarray) else y,
+                    dtype=np.float64).reshape(-1)
+    group = {"cv_idx": cv_idx, "objectives": objectives, "rolls": [r for _, _, r in params]}
+    if X_holdout is None:
+        Xv = X.design() if isinstance(X, LagFrame) else _host_matrix(X)
+    elif np.ndim(X_holdout) == 1:
+        hold = np.asarray(X_holdout, dtype=np.int64)
+        setup = np.setdiff1d(np.arange(len(yv)), hold)
+        group.update(cv_idx=[(setup[np.asarray(tr)], setup[np.asarray(te)]) for tr, te in cv_idx],
+                     refit_rows=setup, holdout_rows=hold)
+        Xv = X.design() if isinstance(X, LagFrame) else _host_matrix(X)
+    else:
+        if list(X_holdout.columns) != list(X.columns):
+            raise ValueError("X_holdout must have the columns of X")
+        yh = np.asarray(y_holdout.values if hasattr(y_holdout, "values") else y_holdout,
+                        dtype=np.float64).reshape(-1)
+        n0 = len(yv)
+        Xv = np.vstack([_host_matrix(X), _host_matrix(X_holdout)])
+        yv = np.concatenate([yv, yh])
+        group.update(refit_rows=np.arange(n0), holdout_rows=n0 + np.arange(len(yh)))
+    res = _grid.run_multi(Xv, yv, [group], score_method=score_method, drop_sets=drops)[0]
+    key = 'cv_R2_score' if score_method == 'r2' else 'cv_mean_score'
+    out = {}
+    for lo, drop, rs in zip(left_out_list, drops, res):
+        full = [reduce_cv_result(r, drop, kw, mn) for (mn, kw, _), r in zip(params, rs)]
+        best = None
+        for i, d in enumerate(full):                 # first strict max (sglm_cv.py:402-415)
+            if d[key] > (-np.inf if best is None else full[best][key]):
+                best = i
+        b = full[best] if best is not None else {"cv_std_score": None, "glm_kwargs": None,
+                                                 "model": None}
+        cv_results = {'best_score': b[key] if best is not None else -np.inf,
+                      'best_score_std': b["cv_std_score"], 'best_params': b["glm_kwargs"],
+                      'best_model': b["model"], 'full_cv_results': full}
+        tup = (cv_results['best_score'], cv_results['best_score_std'],
+               cv_results['best_params'], cv_results['best_model'], cv_results)
+        if X_holdout is not None:
+            tup += (b.get("holdout_score"), b.get("holdout_neg_mse_score"))
+        out[tuple(lo)] = tup
+        if verbose > 0:
+            print(f"left out {lo}: best {key} {cv_results['best_score']}")
+    return out
+
+
 def print_best_model_info(X_setup, best_score, best_params, best_model, start):
     """backend/sglm_ez.py:595-628."""
     print('\n---\n')

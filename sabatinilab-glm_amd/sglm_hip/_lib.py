@@ -101,6 +101,12 @@ SIGNATURES = {
     "sglm_chol64_minnorm_work_bytes": (_sz, [_i32, _i32]),
     "sglm_chol64_minnorm": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp,
                                       _vp, _vp]),
+    "sglm_chol64_drop_kmax": (_i32, []),
+    "sglm_chol64_drop_work_bytes": (_sz, [_i32, _i32, _i32]),
+    "sglm_chol64_drop_prep": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp,
+                                        _vp, _vp]),
+    "sglm_chol64_drop_solve_add": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                             _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sglm_step_scalars": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "sglm_step_update": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sglm_aa_step": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

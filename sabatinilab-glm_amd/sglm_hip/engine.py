@@ -28,6 +28,7 @@ import ctypes
 import math
 import os
 import threading
+import types
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -1352,6 +1353,7 @@ class FitReq:
     max_iter: int = 100
     coef0: Optional[np.ndarray] = None
     intercept0: Optional[float] = None
+    drop: int = -1                  # index into the call's drop-set table (< 0: the full model)
 
 
 @dataclass
@@ -1382,6 +1384,8 @@ class IrlsStats:
     rank_grams: int = 0         # exact mask Grams for the rank decisions of unpenalised fits
     chain_host_s: float = 0.0   # host time spent enqueueing the factorisation chains
     aa_fit_iters: int = 0       # fit-iterations whose direction took the secant correction
+    drop_reduced: int = 0       # drop-set fits solved off the full model's factor (reduced solve)
+    drop_excluded: int = 0      # drop-set fits solved on a factor of their own (exclusion route)
     # flop actually executed by the algorithm, summed over fit-iterations: each computed Gram at
     # the count of the kernel that formed it (dense: n p'(p'+1); event-structured: LagStructure
     # flop1; event correlations: their histogram adds), new factors p'^3/3, gradient / eta /
@@ -1636,8 +1640,13 @@ def syrk6_splits(wgs1: int, nsteps: int, nact: int, P: int, slots: int = 1024) -
 
 
 def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
-         stats: Optional[IrlsStats] = None, bufs: Optional[_Buffers] = None, comm=None):
+         stats: Optional[IrlsStats] = None, bufs: Optional[_Buffers] = None, comm=None,
+         drop_sets=None):
     """Run the batched damped-Newton (IRLS) solve; returns (results, final eta tensor).
+
+    ``drop_sets`` (a list of design column-index lists): the table the requests' ``drop``
+    fields index -- a fit with ``drop >= 0`` is the fit on the design with those columns
+    removed (squared loss on the Gram-space path only, see _gram_ls_drop).
 
     ``comm`` (sglm_hip.comm.RowComm / SimComm): the problem holds one slab of the rows of a
     row-sharded solve; sums over rows are all-reduced, maxima over rows max-reduced, and the
@@ -1650,6 +1659,9 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     fam, power = reqs[0].family, float(reqs[0].power)
     if any(r.family != fam or float(r.power) != power for r in reqs):
         raise ValueError("irls(): one loss family per batch")
+    if any(r.drop >= 0 for r in reqs):
+        _drop_check(prob, reqs, drop_sets)
+        return _gram_ls_drop(prob, reqs, drop_sets, stats, comm)
     if (fam == FAM_SQUARED and GRAM_LS and d.xbits is not None
             and max(prob.mask_count(int(r.mask)) for r in reqs) < 2 ** 24):
         return _gram_ls(prob, reqs, stats, bufs, comm)
@@ -2851,6 +2863,312 @@ def _gram_ls(prob: Problem, reqs: List[FitReq], stats: Optional[IrlsStats], bufs
     return res, bf.eta
 
 
+# device bytes one chunk of a drop-set solve may take for its per-fit row buffers ([fits][ld]
+# predictors and weights, [fits][P][P] Gram slots); the factors and the reduced solves' W blocks
+# of a chunk of keys stay within GRAM_LS_FACTOR_BYTES
+GRAM_LS_DROP_BYTES = float(os.environ.get("SGLM_GRAM_LS_DROP_BYTES", "8e9"))
+
+
+def _drop_check(prob: Problem, reqs: List[FitReq], drop_sets):
+    """Refuse drop-set requests on every path but the Gram-space squared-loss one."""
+    from .estimators import NotYetImplementedError
+    d = prob.design
+    if drop_sets is None:
+        raise ValueError("requests with drop >= 0 need the drop_sets table")
+    if any(r.drop >= len(drop_sets) for r in reqs):
+        raise ValueError("a request's drop index is outside the drop_sets table")
+    if any(r.family != FAM_SQUARED for r in reqs):
+        raise NotYetImplementedError("drop sets on the log-link IRLS path (Poisson / Gamma / "
+                                     "Tweedie objectives): squared loss only")
+    if d.xbits is None:
+        raise NotYetImplementedError("drop sets on the f32-design path (a design that is "
+                                     "neither 0/1 nor mixed)")
+    if not GRAM_LS:
+        raise NotYetImplementedError("drop sets on the IRLS squared-loss path (SGLM_GRAM_LS=0)")
+    if max(prob.mask_count(int(r.mask)) for r in reqs) >= 2 ** 24:
+        raise NotYetImplementedError("drop sets on the IRLS squared-loss path (a row mask of "
+                                     "2^24 rows or more)")
+    for s in drop_sets:
+        a = np.asarray(s, dtype=np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= d.p):
+            raise ValueError(f"drop set column outside [0, {d.p})")
+
+
+def _gram_ls_drop(prob: Problem, reqs: List[FitReq], drop_sets, stats: Optional[IrlsStats], comm,
+                  sets=None):
+    """_gram_ls for a batch with drop sets (the reference drivers' leave_one_out_list loop): fit
+    k is the squared-loss fit on the design WITHOUT the columns drop_sets[reqs[k].drop].  One
+    exact Gram per row mask and one X^T (m y) per (response, mask) serve the full model and every
+    reduced one -- a reduced model's normal equations are a principal submatrix.
+
+    Routes.  A fit with a drop set is solved off the float64 factor of its (mask, penalty,
+    intercept) key -- the full model's -- by sglm_chol64_drop_prep / _drop_solve_add (the
+    reduced-solve route) when that factor has no dependent or zero coordinate, the set has at
+    most sglm_chol64_drop_kmax() columns and the prep status is 0.  Every other one takes the
+    exclusion route: a factor keyed (mask, penalty, intercept, drop) with the dropped columns
+    excluded through dshift, then the minimum-norm projection of the unpenalised fits (lstsq on
+    the remaining columns).  SGLM_DROP_ROUTE=exclude forces the exclusion route.  Either way
+    the fit's dshift row has -1 on its dropped columns, so the refinement residuals and eta see
+    them as absent and the coefficients there are exact zeros.
+
+    Memory.  The batch buffers hold one chunk of Gram slots (a slot per row mask) and the eta rows
+    one chunk of fits, each within GRAM_LS_DROP_BYTES; the factors and W blocks are one chunk of
+    keys' (GRAM_LS_FACTOR_BYTES); the mask Grams stay ([masks][P][P] f32).  What grows with fits
+    x drop sets is the per-fit float64 coefficient, shift and penalty rows ([fits][P]) only.  ``sets`` (the
+    score masks per fit): the fits are scored chunk by chunk and (results, score sums [B, 2, 2])
+    is returned; without it (results, eta [B][ld])."""
+    d = prob.design
+    B0, P, ld, n, p = len(reqs), d.P, d.ld, d.n, d.p
+    dev = d.device
+    st = _stream()
+    up = _Uploads(dev)
+    route = os.environ.get("SGLM_DROP_ROUTE", "auto")
+    if route not in ("auto", "exclude"):
+        raise ValueError(f"SGLM_DROP_ROUTE={route!r}: auto or exclude")
+    kcap = _lib.query("sglm_chol64_drop_kmax")
+    dsets = [np.unique(np.asarray(s, dtype=np.int64).reshape(-1)) for s in drop_sets]
+    drop = np.array([r.drop if r.drop >= 0 and dsets[r.drop].size else -1 for r in reqs],
+                    dtype=np.int64)
+    fmask_h = np.array([r.mask for r in reqs], dtype=np.int32)
+    lam = np.array([float(r.lam) for r in reqs])
+    fi = np.array([1.0 if r.fit_intercept else 0.0 for r in reqs])
+    lam0 = lam == 0.0
+    # keys of the full models' factors, the unpenalised first (as _gram_ls orders them)
+    um = sorted(set(int(m) for m in fmask_h))
+    mi = {m: i for i, m in enumerate(um)}
+    nm = len(um)
+    keys, k_h, k_lam, k_fi = {}, [], [], []
+    bkey = np.zeros(B0, dtype=np.int64)
+    for k in np.argsort(~lam0, kind="stable"):
+        key = (int(fmask_h[k]), float(lam[k]), bool(fi[k]))
+        if key not in keys:
+            keys[key] = len(k_h)
+            k_h.append(mi[key[0]])
+            k_lam.append(key[1])
+            k_fi.append(fi[k])
+        bkey[k] = keys[key]
+    nk = len(k_h)
+    k_h = np.asarray(k_h, dtype=np.int64)
+    # per-fit penalty rows and coordinate shifts (rows B0 ..: the keys' own, nothing dropped)
+    scal = torch.from_numpy(np.concatenate([lam, k_lam, fi, k_fi])).to(dev)
+    lam_d, fi_d = scal[:B0 + nk], scal[B0 + nk:]
+    dshift = torch.full((B0 + nk, P), -1.0, dtype=torch.float32, device=dev)
+    dshift[:, :p] = lam_d[:, None]
+    dshift[:, p] = fi_d - 1.0
+    lamp_d = torch.zeros((B0 + nk, P), dtype=torch.float64, device=dev)
+    lamp_d[:, :p] = lam_d[:, None]
+    hasdrop = np.flatnonzero(drop >= 0)
+    if hasdrop.size:
+        dm = np.zeros((len(dsets), P), dtype=bool)
+        for i, s in enumerate(dsets):
+            dm[i, s] = True
+        dm_d = torch.from_numpy(dm).to(dev)
+        rows_d = torch.from_numpy(hasdrop).to(dev)
+        sub = dshift[rows_d]
+        sub[dm_d[torch.from_numpy(drop[hasdrop]).to(dev)]] = -1.0
+        dshift[rows_d] = sub
+    # the batch buffers of one chunk of Gram slots (one per mask), the eta rows of one chunk of
+    # fits
+    per_slot = 16.0 * ld + (8.0 if SOLVE_INV else 4.0) * P * P + 64.0 * P
+    Bc = int(max(1, min(nm, GRAM_LS_DROP_BYTES // per_slot)))
+    Ec = int(max(1, min(B0, GRAM_LS_DROP_BYTES // (4.0 * ld))))
+    bf = _scratch().buf.get(Bc, P, ld, dev)
+    bf.prob, bf.up, bf.fit_mask_d = prob, up, None
+    # one exact Gram per distinct mask (weights = the mask's multiplicities), in chunks of slots
+    Hm = torch.empty((nm, P, P), dtype=torch.float32, device=dev)
+    mixS = {}
+    nsteps = (n + 31) // 32
+    ntile1 = (P // 256) * (P // 256 + 1) // 2
+    for a in range(0, nm, Bc):
+        ms = um[a:a + Bc]
+        m = len(ms)
+        fm = np.zeros(Bc, dtype=np.int32)
+        fm[:m] = ms
+        bf.fit_mask = fm
+        bf.mixS = {}
+        bf.W[:m] = prob.M[up(np.asarray(ms), np.int64)].float()
+        grows = np.array([float(prob.mask_nnz(q)) if comm is not None else prob.mask_count(q)
+                          for q in ms])
+        _syrk(d, bf, np.arange(m, dtype=np.int32), nsteps, ntile1, stats, st, exact=True,
+              rows=grows)
+        if comm is not None:
+            for k in range(m):
+                comm.sum_(bf.H[k])
+                if k in bf.mixS:
+                    comm.sum_(bf.mixS[k])
+        Hm[a:a + m].copy_(bf.H[:m])
+        for k in range(m):
+            if k in bf.mixS:
+                mixS[a + k] = bf.mixS[k].clone()
+    bf.mixS = None
+    # X^T (m y) of every distinct (response, mask), exact to float64 rounding
+    pairs = sorted(set((int(r.resp), int(r.mask)) for r in reqs))
+    pidx = {pr: i for i, pr in enumerate(pairs)}
+    c = torch.empty((len(pairs), P), dtype=torch.float64, device=dev)
+    xtv_digits(d, prob.M, prob.y64_rows(), pairs, c)
+    if comm is not None:
+        comm.sum_(c)
+    cidx = np.array([pidx[(int(r.resp), int(r.mask))] for r in reqs], dtype=np.int32)
+    # what _Factor64 reads of the batch buffers: the mask Grams, the shift rows, the mixed rows
+    src = types.SimpleNamespace(H=Hm, dshift=dshift, mixS=mixS, up=up, prob=prob,
+                                fit_mask=np.asarray(um, dtype=np.int32))
+    x = torch.zeros((B0, P), dtype=torch.float64, device=dev)
+    res_d = torch.empty_like(x)
+    ndep = torch.zeros(B0, dtype=torch.float64, device=dev)
+    cmap = d._mix["cmap"] if d.cont is not None else None
+    k_c = d.k if d.cont is not None else 0
+
+    def solve(f64, hsrc, sel, fsrc, red=None):
+        """x[sel] = the solve on factors fsrc (of Grams hsrc) plus GRAM_LS_REFINE refinements;
+        red = (pair per fit, the prep's argument tail): the reduced solve."""
+        nq = int(sel.size)
+        if nq == 0:
+            return
+        parts = [sel, fsrc, cidx[sel], hsrc] + ([red[0]] if red is not None else [])
+        ints = up(np.concatenate(parts).astype(np.int32))
+        fits_d, fsrc_d, csrc_d = ints[:nq], ints[nq:2 * nq], ints[2 * nq:3 * nq]
+        hsrc_d = ints[3 * nq:3 * nq + len(hsrc)]
+        psrc_d = ints[3 * nq + len(hsrc):]
+
+        def add(gsrc, g):
+            if red is None:
+                _lib.call("sglm_chol64_solve_add", _p(f64.U), P, _p(f64.state), _p(fits_d),
+                          _p(fsrc_d), _p(gsrc), nq, _p(g), _p(x), st)
+            else:
+                _lib.call("sglm_chol64_drop_solve_add", _p(f64.U), P, _p(f64.state), _p(fits_d),
+                          _p(fsrc_d), _p(gsrc), _p(psrc_d), nq, _p(g), _p(x), *red[1], st)
+
+        add(csrc_d, c)
+        S = f64._S
+        for _ in range(GRAM_LS_REFINE):
+            _lib.call("sglm_chol64_resid", _p(Hm), P, _p(hsrc_d), _p(S),
+                      k_c if S is not None else 0, _p(cmap) if S is not None else None,
+                      _p(fits_d), _p(fsrc_d), _p(csrc_d), nq, _p(c), _p(lamp_d), _p(dshift),
+                      _p(x), _p(res_d), st)
+            add(None, res_d)
+        ndep[fits_d.long()] = f64.counts[:, 1][fsrc_d.long()].to(torch.float64)
+
+    # ---- the full models' factors: the fits without a drop set and the reduced solves
+    red_ok = (drop >= 0) & (route == "auto") & np.array(
+        [dsets[q].size <= kcap if q >= 0 else False for q in drop])
+    fit_status = None
+    if red_ok.any():
+        used = sorted(set(int(q) for q in drop[red_ok]))
+        gidx = {q: i for i, q in enumerate(used)}
+        kmax = max(dsets[q].size for q in used)
+        tab = np.zeros((len(used), kmax), dtype=np.int32)
+        for i, q in enumerate(used):
+            tab[i, :dsets[q].size] = dsets[q]
+        sets_d = torch.from_numpy(tab).to(dev)
+        lens_d = torch.tensor([dsets[q].size for q in used], dtype=torch.int32, device=dev)
+        fit_status = torch.zeros(B0, dtype=torch.int32, device=dev)
+    plain = drop < 0
+    on_base = plain | red_ok
+    npk = np.zeros(nk, dtype=np.int64)              # (key, drop set) pairs per key
+    for k in range(nk):
+        npk[k] = len(set(drop[(bkey == k) & red_ok].tolist()))
+    pair_bytes = _lib.query("sglm_chol64_drop_work_bytes", P, 1, kmax) if red_ok.any() else 0
+    per_key = 16.0 * P * P + float(npk.max(initial=0)) * pair_bytes
+    per = max(1, int(GRAM_LS_FACTOR_BYTES // per_key))
+    for a in range(0, nk, per):
+        b = min(nk, a + per)
+        inch = (bkey >= a) & (bkey < b) & on_base
+        if not inch.any():
+            continue
+        f64 = _Factor64(d, src, k_h[a:b], B0 + np.arange(a, b), lamp_d, st)
+        sel = np.flatnonzero(inch & plain)
+        solve(f64, k_h[a:b], sel, bkey[sel] - a)
+        pf = sel[lam0[sel]]
+        f64.minnorm(d, src, pf, bkey[pf] - a, x, st)
+        sel = np.flatnonzero(inch & red_ok)
+        if sel.size:
+            pr = sorted(set(zip((bkey[sel] - a).tolist(), drop[sel].tolist())))
+            pri = {q: i for i, q in enumerate(pr)}
+            npair = len(pr)
+            pint = up(np.array([[q[0] for q in pr], [gidx[q[1]] for q in pr]], dtype=np.int32))
+            work = _work(_lib.query("sglm_chol64_drop_work_bytes", P, npair, kmax), dev, "drop")
+            status = torch.empty(npair, dtype=torch.int32, device=dev)
+            _lib.call("sglm_chol64_drop_prep", _p(f64.U), P, _p(f64.state), _p(f64.counts),
+                      _p(pint[0]), _p(pint[1]), npair, _p(sets_d), _p(lens_d), kmax, _p(work),
+                      _p(status), st)
+            psrc = np.array([pri[(int(bkey[k] - a), int(drop[k]))] for k in sel], dtype=np.int32)
+            solve(f64, k_h[a:b], sel, bkey[sel] - a,
+                  red=(psrc, (_p(pint[1]), npair, _p(sets_d), _p(lens_d), kmax, _p(work),
+                              _p(status))))
+            fit_status[torch.from_numpy(sel).to(dev)] = status[torch.from_numpy(psrc).to(
+                dev).long()]
+        del f64
+    # the one extra readback: which reduced solves the device refused
+    excl = (drop >= 0) & ~red_ok
+    if fit_status is not None:
+        failed = (fit_status.cpu().numpy() != 0) & red_ok
+        up.synced()
+        excl |= failed
+        red_ok = red_ok & ~failed
+    # ---- the exclusion route: a factor per (mask, penalty, intercept, drop set)
+    ekeys, e_h, e_d = {}, [], []
+    ekey = np.full(B0, -1, dtype=np.int64)
+    for k in np.flatnonzero(excl):
+        key = (int(fmask_h[k]), float(lam[k]), bool(fi[k]), int(drop[k]))
+        if key not in ekeys:
+            ekeys[key] = len(e_h)
+            e_h.append(mi[key[0]])
+            e_d.append(int(k))
+        ekey[k] = ekeys[key]
+    e_h, e_d = np.asarray(e_h, dtype=np.int64), np.asarray(e_d, dtype=np.int64)
+    per = max(1, int(GRAM_LS_FACTOR_BYTES // (16.0 * P * P)))
+    for a in range(0, len(e_h), per):
+        b = min(len(e_h), a + per)
+        sel = np.flatnonzero((ekey >= a) & (ekey < b))
+        f64 = _Factor64(d, src, e_h[a:b], e_d[a:b], lamp_d, st)
+        solve(f64, e_h[a:b], sel, ekey[sel] - a)
+        pf = sel[lam0[sel]]
+        f64.minnorm(d, src, pf, ekey[pf] - a, x, st)
+        del f64
+    # ---- eta (and the scores) in chunks of fits
+    beta32 = x.float()
+    fam, power = reqs[0].family, float(reqs[0].power)
+    if sets is None:
+        eta = torch.empty((B0, ld), dtype=torch.float32, device=dev)
+        for a in range(0, B0, Ec):
+            d.eta(beta32[a:a + Ec], eta[a:a + Ec])
+        ret = eta
+    else:
+        sets = np.asarray(sets, dtype=np.int32).reshape(B0, 2)
+        ret = np.zeros((B0, 2, 2))
+        eta = _work(4 * Ec * ld, dev, "drop_eta")[:4 * Ec * ld].view(torch.float32).view(Ec, ld)
+        for a in range(0, B0, Ec):
+            b = min(B0, a + Ec)
+            d.eta(beta32[a:b], eta[:b - a])
+            ret[a:b] = score_sums(prob, fam, power, eta, [int(r.resp) for r in reqs[a:b]],
+                                  sets[a:b], comm=comm)
+    outs = torch.cat([x.reshape(-1), ndep]).cpu().numpy()
+    if stats is not None:
+        stats.newton_iters += 1
+        stats.fit_iters += B0
+        stats.gram_fits += nm
+        stats.gram_fit_iters += nm
+        stats.rank_grams += nm
+        stats.roundtrips += 2 if fit_status is not None else 1
+        stats.stops["tol"] += B0
+        stats.drop_reduced += int(red_ok.sum())
+        stats.drop_excluded += int(excl.sum())
+        pa = float(p + 1)
+        kk = np.array([dsets[q].size for q in drop[red_ok]], dtype=np.float64)
+        stats.alg_flop += float((nk + len(e_h)) * pa ** 3 / 3
+                                + B0 * (1 + GRAM_LS_REFINE) * 4 * pa * pa
+                                + np.sum(pa * pa * kk / 3 + pa * kk * kk))
+    xb = outs[: B0 * P].reshape(B0, P)
+    cnt = outs[B0 * P:].astype(np.int64)
+    bf.prob = bf.up = bf.fit_mask = None
+    res = []
+    for k, r in enumerate(reqs):
+        res.append(FitResult(coef=xb[k, :p].copy(),
+                             intercept=float(xb[k, p]) if r.fit_intercept else 0.0,
+                             n_iter=1 + GRAM_LS_REFINE, converged=True, dropped=int(cnt[k])))
+    return res, ret
+
+
 IRLS_GROUPS = int(__import__("os").environ.get("SGLM_IRLS_GROUPS", "1"))
 IRLS_GROUP_MIN = int(__import__("os").environ.get("SGLM_IRLS_GROUP_MIN", "24"))            # fits per group below which the batch is not split
 
@@ -2911,12 +3229,18 @@ def _partition(reqs: List[FitReq], ngroups: int, rows=None) -> List[List[int]]:
 
 
 def irls_scored(prob: Problem, reqs: List[FitReq], sets: np.ndarray,
-                stats: Optional[IrlsStats] = None, ngroups: Optional[int] = None, comm=None):
+                stats: Optional[IrlsStats] = None, ngroups: Optional[int] = None, comm=None,
+                drop_sets=None):
     """IRLS + score sums for a batch, as ``ngroups`` independent fit groups, each driven by
     its own host thread on its own HIP stream.  A group's latency-bound phases (the blocked
     Cholesky chain, the host decisions between iterations) then run while another group's
-    Gram keeps the MFMA busy.  Returns (results, score sums [B, 2, 2]) in request order."""
+    Gram keeps the MFMA busy.  Returns (results, score sums [B, 2, 2]) in request order.
+    Requests with ``drop >= 0`` (``drop_sets``: their table) are solved and scored in chunks by
+    _gram_ls_drop."""
     require_gpu()
+    if any(r.drop >= 0 for r in reqs):
+        _drop_check(prob, reqs, drop_sets)
+        return _gram_ls_drop(prob, reqs, drop_sets, stats, comm, sets=sets)
     ng = IRLS_GROUPS if ngroups is None else int(ngroups)
     fam, power = reqs[0].family, float(reqs[0].power)
     fresp = [r.resp for r in reqs]

@@ -193,16 +193,54 @@ def merge_results(local: dict, dist=None) -> dict:
 
 def run(X, y, cv_idx, objectives: Sequence[Objective], rolls: Sequence[int],
         score_method: str = "mse", coef0=None, intercept0=None, stats=None, shard=True,
-        simulate=None):
+        simulate=None, drop_sets=None):
     """Return one result dict per objective (reference key set minus glm_kwargs/model).
+
+    ``drop_sets`` (see run_multi): one such list per drop set, in order.
 
     ``simulate=comm.SimComm`` (development only): one rank's slab of a row-sharded grid
     (or, with ``SimComm.recorder()`` and the full design, the recording it replays).
     ``simulate=(rank, world)`` (development only) solves just that rank's share without a
     process group and returns the raw per-fit results instead of the assembled dicts."""
     out = run_multi(X, y, [{"cv_idx": cv_idx, "objectives": objectives, "rolls": rolls}],
-                    score_method, coef0, intercept0, stats, shard, simulate)
+                    score_method, coef0, intercept0, stats, shard, simulate, drop_sets)
     return out if simulate is not None else out[0]
+
+
+def check_drop_sets(drop_sets, p: int, groups=None):
+    """The drop-set table of a grid as sorted lists of distinct column indices below ``p``
+    (host-side validation, no device): ``[]`` is the full model.  With ``groups``, every
+    objective must be a squared-loss one on the IRLS path."""
+    if isinstance(drop_sets, (str, bytes)) or not hasattr(drop_sets, "__iter__"):
+        raise TypeError("drop_sets: a list of column-index lists")
+    out = []
+    for s in drop_sets:
+        if isinstance(s, (str, bytes)) or not hasattr(s, "__iter__"):
+            raise TypeError("drop_sets: every entry is a list of column indices ([] = full model)")
+        a = np.asarray(list(s))
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("drop_sets: column indices must be integers")
+        a = a.astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= p):
+            raise ValueError(f"drop_sets: column index outside [0, {p})")
+        if np.unique(a).size != a.size:
+            raise ValueError("drop_sets: a column is listed twice in one set")
+        if a.size >= p:
+            raise ValueError("drop_sets: a set removes every column")
+        out.append(sorted(int(v) for v in a))
+    if not out:
+        raise ValueError("drop_sets: empty table ([[]] is the full model alone)")
+    if groups is not None and any(out):
+        from .estimators import NotYetImplementedError
+        for g in groups:
+            for o in g["objectives"]:
+                if o.kind == "cd":
+                    raise NotYetImplementedError("drop sets on the coordinate-descent path "
+                                                 "(Lasso / ElasticNet objectives)")
+                if o.family != E.FAM_SQUARED:
+                    raise NotYetImplementedError("drop sets on the log-link IRLS path (Poisson "
+                                                 "/ Gamma / Tweedie objectives)")
+    return out
 
 
 def plan_fits(groups: Sequence[dict], n: int, check: bool = True):
@@ -273,13 +311,20 @@ def rank_share(plan, groups: Sequence[dict], rank: int, world: int):
 
 
 def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=None,
-              intercept0=None, stats=None, shard=True, simulate=None):
+              intercept0=None, stats=None, shard=True, simulate=None, drop_sets=None):
     """Several CV grids over ONE resident design, solved as one batch (SURVEY.md §8(f) 2:
     holdout resplits).  Each group: ``cv_idx`` (global row indices), ``objectives``,
     ``rolls``, optional ``refit_rows`` (the refit's rows; default all) and ``holdout_rows``
     (rows the refits are also scored on).  Returns one list of per-param dicts per group;
     with ``holdout_rows`` every dict also carries ``refit_holdout_r2`` (R^2 / D^2) and
-    ``refit_holdout_neg_mse`` — what ``training_fit_holdout_score`` reports for that param."""
+    ``refit_holdout_neg_mse`` — what ``training_fit_holdout_score`` reports for that param.
+
+    ``drop_sets`` (a list of column-index lists, ``[]`` = the full model; squared-loss IRLS
+    objectives only): the reference drivers' leave_one_out_list loop.  Every fit of the grid is
+    also solved with each set's columns removed, all off ONE resident design, one Gram per row
+    mask and one X^T (m y) per (response, mask) (engine._gram_ls_drop).  Each group then returns
+    one list of per-param dicts PER DROP SET, in order; ``cv_coefs`` / ``refit_coef`` keep the
+    full length p with exact zeros on the dropped columns.  ``None``: exactly today's return."""
     import time
     tick = stats.mark if (stats is not None and (stats.trace_phases or stats.host_phases)) \
         else (lambda name, t: t)
@@ -296,6 +341,11 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
         # (Design.from_events / from_host with slab=grid.rank_slab(n)) -- a full Design in a
         # process group is sharded by fits instead
         comm = RowComm(dist)
+    dsets = None
+    if drop_sets is not None:
+        dsets = check_drop_sets(drop_sets, X.p if isinstance(X, E.Design)
+                                else int(np.asarray(X).shape[1]), groups)
+    nds = 1 if dsets is None else len(dsets)
     if isinstance(X, E.Design):
         design = X
     else:
@@ -372,7 +422,10 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
         solve_groups.setdefault(key, []).append(i)
     for key, idxs in solve_groups.items():
         reqs = []
-        for i in idxs:
+        if dsets is not None:
+            # every drop variant of a fit-table row next to it (and so on the row's rank)
+            idxs = [i for i in idxs for _ in range(nds)]
+        for v, i in enumerate(idxs):
             _, _, _, m, r, _ = table[i]
             obj = objective(i)
             cnt = counts[m]
@@ -380,6 +433,8 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
                                  obj.fit_intercept, obj.max_iter,
                                  None if coef0 is None else np.asarray(coef0, float),
                                  None if intercept0 is None else float(intercept0)))
+            if dsets is not None and dsets[v % nds]:
+                reqs[-1].drop = v % nds
         t0 = tick("fit_table", t0)
         sets = np.array([[local[table[i][3]], local.get(table[i][5], -1)] for i in idxs],
                         dtype=np.int32)
@@ -389,7 +444,8 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
             sums = E.score_sums(prob, E.FAM_SQUARED, 0.0, eta, [table[i][4] for i in idxs],
                                 sets)
         else:
-            res, sums = E.irls_scored(prob, reqs, sets, stats=stats, comm=comm)
+            res, sums = E.irls_scored(prob, reqs, sets, stats=stats, comm=comm,
+                                      drop_sets=dsets)
         t0 = tick("solve", t0)
         for q, i in enumerate(idxs):
             rr = res[q]
@@ -408,14 +464,20 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
                 sc["test"] = _score(score_method, obj, sums[q][1], st_te)
                 sc["ss_res"] = float(sums[q][1][0])
                 sc["sst"], sc["cnt_te"] = st_te["sst"], st_te["cnt"]
-            results[i] = (rr.coef, rr.intercept, rr.n_iter, rr.converged, sc)
+            results[i if dsets is None else (i, q % nds)] = (rr.coef, rr.intercept, rr.n_iter,
+                                                             rr.converged, sc)
     t0 = tick("score_sums", t0)
     if simulate is not None:
         return results
     if comm is None:
         results = merge_results(results, dist)
 
-    out_all = assemble(groups, plan, results, p)
+    if dsets is None:
+        out_all = assemble(groups, plan, results, p)
+    else:
+        per = [assemble(groups, plan, {i: results[(i, v)] for i in range(len(table))}, p)
+               for v in range(nds)]
+        out_all = [[per[v][gi] for v in range(nds)] for gi in range(len(groups))]
     tick("assemble", t0)
     return out_all
 
