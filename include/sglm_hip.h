@@ -580,6 +580,28 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
                          const int32_t* fit_resp, const int32_t* fit_mask, const float* t,
                          int32_t T, double* out, float* dmax, void* work, sglm_stream_t stream);
 
+/* sglm_loss_trials_max (T = 5) and the full-step link of the fits in one pass over eta and deta.
+ * For launch row q < B, fit k = slots[q] (q when slots is NULL):
+ *  - out[q][0..5) and dmax[q] are bitwise those of sglm_loss_trials_max on the same inputs
+ *    (the same expressions, row assignment and reduction order);
+ *  - undo[q][i] = eta[k][i] and then eta[k][i] += 1 * deta[k][i] for every i < n, the rows the
+ *    mask leaves out included (undo: B rows of ld floats; a fit that does not take the full step
+ *    is put back from it);
+ *  - row q of the three bf16 piece planes of Rp (plane stride Bp * ld, Bp a multiple of 32 and
+ *    >= B) holds R = M * g(y, eta_new) split as sglm_link_update_rp with step 1 and positions
+ *    0.. writes it, bitwise: 0 where the mask is 0 and on the rows n <= i < ld.
+ * Slots that are not listed are not touched.  `work`: sglm_rowsum_work_bytes(B, 5, n).
+ * With out == NULL and dmax == NULL the call is the link alone (undo, eta and Rp as above, no
+ * sums; t, T and work are not read): what engine.irls enqueues behind the read-back of
+ * sglm_loss_trials_max's sums, so that the link runs while the host decides the steps.
+ * SGLM_EINVAL on a null pointer (one of out / dmax alone included), T != 5 with sums, Bp < B or
+ * Bp % 32, n outside 1..ld, ld % 256. */
+int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
+                          const int32_t* slots, float* eta, const float* deta, const float* Y,
+                          const uint8_t* M, const int32_t* fit_resp, const int32_t* fit_mask,
+                          const float* t, int32_t T, double* out, float* dmax, float* undo,
+                          void* Rp, int32_t Bp, void* work, sglm_stream_t stream);
+
 /* eta[k][i] += step[q] * deta[k][i], k = slots[q] (q when slots is NULL), q < B
  * (host-chosen step per fit, device array). */
 int sglm_eta_axpy(int64_t n, int64_t ld, int32_t B, const int32_t* slots, const float* step,

@@ -418,6 +418,173 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
     }
 }
 
+// loss_trials_kernel (with dmax) and link_kernel at step 1 in one pass over eta and deta: the
+// line search accepts the full step almost always, so the predictor update and the packed R of
+// the next gradient are written while the trial sums are formed, and the rare fit that takes
+// another step is put back from `undo`.  Per (chunk, launch row q, fit k = slots[q]):
+//  - part / dmax: the expressions, per-thread row order and reductions of loss_trials_kernel;
+//  - undo[q][i] = eta[k][i], then eta[k][i] += 1 * deta[k][i] for every i < n (masked-out rows
+//    too: the scores read them);
+//  - Rp row q of each piece plane (stride Bp * ld) = split3(m * half_loss(eta_new).g), as
+//    link_kernel forms it from the stored predictor; 0 where m == 0 and on the rows n..ld-1
+//    (the last chunk's block writes those).
+// A quad of four masked-out rows skips only the losses.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+template <bool LOSS>
+__global__ void __launch_bounds__(256) loss_trials_link_kernel(
+    int32_t family, float power, int64_t n, int64_t ld, float* __restrict__ eta,
+    const float* __restrict__ deta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
+    const int32_t* __restrict__ fit_resp, const int32_t* __restrict__ fit_mask,
+    const float* __restrict__ tv, int32_t T, double* __restrict__ part,
+    float* __restrict__ dmax, const int32_t* __restrict__ slots, float* __restrict__ undo,
+    __bf16* __restrict__ Rp, int32_t Bp) {
+    __shared__ double sh[4];
+    __shared__ float shm[4];
+    const int q = blockIdx.y;                       // output row = packed R row = undo row
+    const int k = slots ? slots[q] : q;             // fit slot
+    const int32_t nchunks = gridDim.x;
+    float* e = eta + (int64_t)k * ld;
+    const float* d = deta + (int64_t)k * ld;
+    const float* y = Y + (int64_t)fit_resp[k] * ld;
+    const uint8_t* m = M + (int64_t)fit_mask[k] * ld;
+    float* u = undo + (int64_t)q * ld;
+    const int64_t plane = (int64_t)Bp * ld;
+    __bf16* rp = Rp + (int64_t)q * ld;
+    double acc[kMaxTrials];
+    for (int j = 0; j < kMaxTrials; ++j) acc[j] = 0.0;
+    float mx = 0.0f;
+    const int64_t i0 = (int64_t)blockIdx.x * kRowChunk;
+    const int64_t i1 = min(i0 + kRowChunk, n);
+    // R of one row from the updated predictor, as link_kernel forms it
+    auto link_row = [&](float mf, float yi, float en) {
+        const LossOut o = half_loss(family, power, yi, en);
+        return mf * o.g;
+    };
+    auto store_r = [&](int64_t i, float ri) {
+        __bf16 hi, mid, lo;
+        split3(ri, hi, mid, lo);
+        rp[i] = hi;
+        rp[plane + i] = mid;
+        rp[2 * plane + i] = lo;
+    };
+    // LOSS = false: the link alone (no sums, tv / part / dmax not touched), four rows at a time
+    bool halving = !LOSS;
+    if constexpr (LOSS)
+        halving = family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f && T == 5 && tv[0] == 0.0f &&
+                  tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f && tv[4] == 0.125f;
+    if (halving) {
+        auto row = [&](double mi, float yi, float ei, float di) {
+            mx = fmaxf(mx, fabsf(di));
+            const float muf = expf(ei), x8 = expm1f(0.125f * di);
+            const float x4 = x8 * (2.0f + x8), x2 = x4 * (2.0f + x4), x1 = x2 * (2.0f + x2);
+            const double mu = muf, yd = (double)yi * (double)di;
+            acc[0] += mi * (mu - (double)yi * (double)ei);
+            acc[1] += mi * (mu * (double)x1 - yd);
+            acc[2] += mi * (mu * (double)x2 - 0.5 * yd);
+            acc[3] += mi * (mu * (double)x4 - 0.25 * yd);
+            acc[4] += mi * (mu * (double)x8 - 0.125 * yd);
+        };
+        auto one = [&](int64_t r) {                 // the chunk's last rows, one at a time
+            const float eo = e[r], dr = d[r];
+            const float en = eo + 1.0f * dr;
+            u[r] = eo;
+            e[r] = en;
+            const uint32_t mb = m[r];
+            float ri = 0.0f;
+            if (mb != 0u) {
+                const float yr = y[r];
+                if constexpr (LOSS) row((double)mb, yr, eo, dr);
+                ri = link_row((float)mb, yr, en);
+            }
+            store_r(r, ri);
+        };
+        // four consecutive rows per thread as in loss_trials_kernel; the next quad's mask,
+        // eta and deta are loaded before this quad's arithmetic and stores
+        int64_t i = i0 + 4 * threadIdx.x;
+        uint32_t m4n = 0u;
+        f32x4 e4n = {}, d4n = {};
+        if (i + 4 <= i1) {
+            m4n = *reinterpret_cast<const uint32_t*>(m + i);
+            e4n = *reinterpret_cast<const f32x4*>(e + i);
+            d4n = *reinterpret_cast<const f32x4*>(d + i);
+        }
+        for (; i < i1; i += 1024) {
+            if (i + 4 <= i1) {
+                const uint32_t m4 = m4n;
+                const f32x4 e4 = e4n, d4 = d4n;
+                if (i + 1024 + 4 <= i1) {
+                    m4n = *reinterpret_cast<const uint32_t*>(m + i + 1024);
+                    e4n = *reinterpret_cast<const f32x4*>(e + i + 1024);
+                    d4n = *reinterpret_cast<const f32x4*>(d + i + 1024);
+                }
+                f32x4 en;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) en[j] = e4[j] + 1.0f * d4[j];
+                *reinterpret_cast<f32x4*>(u + i) = e4;
+                *reinterpret_cast<f32x4*>(e + i) = en;
+                float r4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (m4 != 0u) {
+                    const f32x4 y4 = *reinterpret_cast<const f32x4*>(y + i);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t mb = (m4 >> (8 * j)) & 0xffu;
+                        if (mb != 0u) {
+                            if constexpr (LOSS) row((double)mb, y4[j], e4[j], d4[j]);
+                            r4[j] = link_row((float)mb, y4[j], en[j]);
+                        }
+                    }
+                }
+                bf16x4 hi4, mid4, lo4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    __bf16 hi, mid, lo;
+                    split3(r4[j], hi, mid, lo);
+                    hi4[j] = hi; mid4[j] = mid; lo4[j] = lo;
+                }
+                *reinterpret_cast<bf16x4*>(rp + i) = hi4;
+                *reinterpret_cast<bf16x4*>(rp + plane + i) = mid4;
+                *reinterpret_cast<bf16x4*>(rp + 2 * plane + i) = lo4;
+            } else {
+                for (int64_t r = i; r < i1; ++r) one(r);
+            }
+        }
+    } else {
+        for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+            const float eo = e[i], dr = d[i];
+            const float en = eo + 1.0f * dr;
+            u[i] = eo;
+            e[i] = en;
+            const double mi = (double)m[i];
+            float ri = 0.0f;
+            if (mi != 0.0) {
+                const float yr = y[i];
+                const double yi = yr, ei = eo, di = dr;
+                mx = fmaxf(mx, fabsf((float)di));
+                for (int j = 0; j < T; ++j)
+                    acc[j] += mi * half_loss_d(family, (double)power, yi, ei + (double)tv[j] * di);
+                ri = link_row((float)m[i], yr, en);
+            }
+            store_r(i, ri);
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1)                // the padding rows of the packed R
+        for (int64_t i = n + threadIdx.x; i < ld; i += 256) store_r(i, 0.0f);
+    if constexpr (!LOSS) return;
+    double s0 = 0.0;
+    for (int j = 0; j < T; ++j) {
+        double s = block_sum_d(acc[j], sh);
+        if (j == 0) s0 = s;
+        else if (halving) s += s0;
+        if (threadIdx.x == 0) part[((int64_t)q * T + j) * nchunks + blockIdx.x] = s;
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        atomicMax(reinterpret_cast<unsigned int*>(dmax + q),
+                  __float_as_uint(fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]))));
+}
+
 __global__ void __launch_bounds__(256) score_kernel(
     int32_t family, float power, int64_t n, int64_t ld, const float* __restrict__ eta,
     const float* __restrict__ Y, const uint8_t* __restrict__ M,
@@ -1152,6 +1319,41 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
     }
     loss_trials_kernel<<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
     int st = check_launch("loss_trials_kernel");
+    if (st) return st;
+    const int64_t rows = (int64_t)B * T;
+    reduce_chunks_d<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);
+    return check_launch("reduce_chunks_d");
+}
+
+int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
+                          const int32_t* slots, float* eta, const float* deta, const float* Y,
+                          const uint8_t* M, const int32_t* fit_resp, const int32_t* fit_mask,
+                          const float* t, int32_t T, double* out, float* dmax, float* undo,
+                          void* Rp, int32_t Bp, void* work, sglm_stream_t stream) {
+    if (B <= 0) return SGLM_OK;
+    const bool link_only = !out && !dmax;           // the sums were taken by another call
+    if (!eta || !deta || !Y || !M || !fit_resp || !fit_mask || !undo || !Rp || Bp < B ||
+        Bp % 32 || n <= 0 || n > ld || ld % 256 ||
+        (!link_only && (T != 5 || !t || !out || !dmax || !work))) {
+        set_error("sglm_loss_trials_link: bad args (T=%d, Bp=%d)", T, Bp);
+        return SGLM_EINVAL;
+    }
+    const int32_t nc = row_chunks(n);
+    hipStream_t s = as_stream(stream);
+    if (link_only) {
+        loss_trials_link_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(
+            family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
+            nullptr, slots, undo, (__bf16*)Rp, Bp);
+        return check_launch("loss_trials_link_kernel<link only>");
+    }
+    if (hipMemsetAsync(dmax, 0, sizeof(float) * (size_t)B, s) != hipSuccess) {
+        set_error("sglm_loss_trials_link: hipMemsetAsync failed");
+        return SGLM_EHIP;
+    }
+    loss_trials_link_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(
+        family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
+        slots, undo, (__bf16*)Rp, Bp);
+    int st = check_launch("loss_trials_link_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
     reduce_chunks_d<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);

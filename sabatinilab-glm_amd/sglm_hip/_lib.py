@@ -121,6 +121,9 @@ SIGNATURES = {
                                    _vp, _vp, _i32, _vp, _vp, _vp]),
     "sglm_loss_trials_max": (C.c_int, [_i32, _f32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "sglm_loss_trials_link": (C.c_int, [_i32, _f32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                        _vp]),
     "sglm_eta_axpy": (C.c_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sglm_eta_axpy_max": (C.c_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sglm_eta_pair_absmax": (C.c_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

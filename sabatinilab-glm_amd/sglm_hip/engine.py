@@ -70,6 +70,20 @@ ETA_FINAL_ITERS = 8
 # runs over every active fit, stopped ones included, and the host still waits for the next
 # Hessian plan's readback behind it, so little host time leaves the critical path
 DEV_DECIDE = __import__("os").environ.get("SGLM_DEV_DECIDE", "0") == "1"
+# the full-step link of every active fit before the host has decided the steps (the line search
+# accepts the full step almost always): sglm_loss_trials_link writes eta += d_eta, an undo copy of
+# the old predictor and the packed R of the next gradient; a fit that takes another step is put
+# back from the undo copy and linked as before, so every result stays bitwise.
+#   2 (default): the link alone, enqueued behind the iteration's read-back -- it runs while the
+#      host waits for the record and reads the verdicts, when the GPU had nothing queued
+#      (C4 grid 27.54 -> 27.01 ms, interleaved in one process, seven blocks of ten grids each)
+#   1: inside the trial-loss pass (eta and d_eta read once).  1.1 ms less kernel time per grid,
+#      but no wall-clock gain (27.58 -> 27.30 ms, less than one deviation of the runs): the
+#      pass's extra 0.15 ms per iteration sits ahead of the read-back, and the separate link it
+#      replaces ran while the host did its bookkeeping
+#   0: the two passes, the link after the host's decisions.
+# Packed-R designs without DEV_DECIDE only.
+STEP_LINK = int(__import__("os").environ.get("SGLM_STEP_LINK", "2") or 0)
 # the Anderson correction as one kernel (sglm_aa_step) instead of ~20 torch operations
 # (C4 grid 35.26 -> 34.69 ms, interleaved A/B with the event-structured Gram)
 AA_KERNEL = __import__("os").environ.get("SGLM_AA_KERNEL", "1") == "1"
@@ -1384,6 +1398,8 @@ class IrlsStats:
     rank_grams: int = 0         # exact mask Grams for the rank decisions of unpenalised fits
     chain_host_s: float = 0.0   # host time spent enqueueing the factorisation chains
     aa_fit_iters: int = 0       # fit-iterations whose direction took the secant correction
+    step_link: int = 0          # fit-iterations whose full step was linked ahead of the decision
+    step_restored: int = 0      # fit-iterations put back from the undo copy of that link
     drop_reduced: int = 0       # drop-set fits solved off the full model's factor (reduced solve)
     drop_excluded: int = 0      # drop-set fits solved on a factor of their own (exclusion route)
     # flop actually executed by the algorithm, summed over fit-iterations: each computed Gram at
@@ -1736,13 +1752,15 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     drift = np.full(B0, np.inf)         # predictor drift since each fit's Hessian was formed
     # one host round trip per Newton iteration: the gradient, the step direction, the trial
     # losses and the step's predictor drift come back together (pinned buffers, async copies)
-    dmax_d = torch.zeros(B0, dtype=torch.float32, device=dev)
-    dmax_h = _pinned("dmax", B0, torch.float32)
-    L_h = _pinned("L", B0 * 8, torch.float64)
     ts_all = torch.empty(ts_h.size, dtype=torch.float64, device=dev)
     ts_all.copy_(scal[3 * B0:])
     nts = int(ts_all.numel())
-    sc_d = torch.empty(B0 * (6 + nts), dtype=torch.float64, device=dev)
+    # ... as ONE device record read back with one copy: Anderson's rm [B0][2] f32 (per slot),
+    # then for the iteration's na active fits the trial sums [na][5] f64, the step scalars
+    # [na][6 + nts] f64 and dmax [na] f32 (the kernels write through pointers into it)
+    rec_aa = 8 * B0
+    rec_d = torch.zeros(rec_aa + 8 * B0 * (5 + 6 + nts) + 4 * B0, dtype=torch.uint8, device=dev)
+    rec_h = _pinned("rec", rec_d.numel(), torch.uint8)
     # fits still at their common start (same mask and response => bitwise equal Hessians)
     fresh_start = np.array([r.coef0 is None for r in reqs])
     gram_now = np.zeros(B0, dtype=bool)
@@ -1802,8 +1820,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         aa_used = torch.zeros((B0, P), dtype=torch.float32, device=dev)
         # per slot, this iteration's raw direction size (max |f_j|, j < p; |f_p|) where the
         # correction ran: convergence is also judged on the raw Newton step
-        aa_rm = torch.zeros((B0, 2), dtype=torch.float32, device=dev)
-        aa_rm_h = _pinned("aa_rm", 2 * B0, torch.float32)
+        aa_rm = rec_d[:rec_aa].view(torch.float32).view(B0, 2)
     aa_t = np.zeros(B0)
     aa_key = np.full(B0, -1, dtype=np.int64)
     fepoch = np.zeros(B0, dtype=np.int64)
@@ -2016,6 +2033,15 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         ev_dec = torch.cuda.Event()
     grad_d, grad_n, grad_bp = None, 0, 0     # the gradient's slots, count and R plane stride
     dev_linked = False                       # this iteration's link ran at the previous one's end
+    # the full-step link ahead of the decisions (STEP_LINK; 1: in the trial-loss pass, 2: alone
+    # behind the read-back, the host then waits for ev_rec): the old predictors of its fits, and
+    # the next gradient's (slots, count, plane stride) over the packed R rows it left in this
+    # iteration's list order
+    step_link = int(STEP_LINK) if (use_rp and fused and not dev_dec) else 0
+    if step_link:
+        ev_rec = torch.cuda.Event()
+        undo = _work(B0 * ld * 4, dev, "undo")[: B0 * ld * 4].view(torch.float32).view(B0, ld)
+    carried = None
 
     import time
     tick = stats.mark if (stats is not None and (stats.trace_phases or stats.host_phases)) \
@@ -2035,7 +2061,11 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             act_d = up(act, np.int32)        # the gradient keeps the device's list (grad_d)
         else:
             act_d = linked if linked is not None else up(act, np.int32)
-            grad_d, grad_n, grad_bp = act_d, na, pad_to(na, 32)
+            if carried is not None:
+                grad_d, grad_n, grad_bp = carried
+                carried = None
+            else:
+                grad_d, grad_n, grad_bp = act_d, na, pad_to(na, 32)
         g_copy = None                        # (fits, their lead fits): gradient rows copied
         link_d, link_n = act_d, na
         if GRAD_DEDUP and use_rp and fused and not dev_linked and linked is None:
@@ -2415,24 +2445,42 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         # per-fit scalars of the line search and the stopping rule, reduced on the device
         # over the coefficients (no B x P array crosses to the host): g.d, the penalty terms
         # lam|w|^2, 2 lam w.d, lam|d|^2, max|d| and max|w + t d| for every trial step t
-        sc = sc_d[: na * (6 + nts)]
+        rec_sc = rec_aa + 8 * na * 5
+        rec_dm = rec_sc + 8 * na * (6 + nts)
+        rec_end = rec_dm + 4 * na
+        Lrec = rec_d[rec_aa:rec_sc].view(torch.float64)
+        sc = rec_d[rec_sc:rec_dm].view(torch.float64)
+        dmax_d = rec_d[rec_dm:rec_end].view(torch.float32)
         _lib.call("sglm_step_scalars", P, P if STOP_LEGACY else p, na, _p(act_d), _p(bf.gtot), _p(beta64_d), _p(bf.delta),
                   _p(lamp_d), _p(ts_all), nts, _p(sc), st)
         t0 = tick("it_solve_eta", t0)
         # ---- line search (rows of L, dmax and sc: active fits in slot order)
-        _lib.call("sglm_loss_trials_max", fam, power, n, ld, na, _p(act_d), _p(bf.eta),
-                  _p(bf.deta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), _p(tv1), 5,
-                  _p(Ltr), _p(dmax_d), _p(xtr_work), st)
+        if step_link == 1:
+            # ... with the full step taken on the way: eta += d_eta (the old predictors kept in
+            # `undo`) and the packed R of the next gradient at the fits' rows of this list
+            _lib.call("sglm_loss_trials_link", fam, power, n, ld, na, _p(act_d), _p(bf.eta),
+                      _p(bf.deta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), _p(tv1),
+                      5, _p(Lrec), _p(dmax_d), _p(undo), _p(rp_buf), pad_to(na, 32),
+                      _p(xtr_work), st)
+        else:
+            _lib.call("sglm_loss_trials_max", fam, power, n, ld, na, _p(act_d), _p(bf.eta),
+                      _p(bf.deta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), _p(tv1),
+                      5, _p(Lrec), _p(dmax_d), _p(xtr_work), st)
         if comm is not None:
-            comm.sum_(Ltr[: na * 5])
-            comm.max_(dmax_d[:na])
-        L_h[: na * 5].copy_(Ltr[: na * 5], non_blocking=True)
-        dmax_h[:na].copy_(dmax_d[:na], non_blocking=True)
-        sc_h = _pinned("sc", sc.numel(), torch.float64)
-        sc_h.copy_(sc, non_blocking=True)
+            comm.sum_(Lrec)
+            comm.max_(dmax_d)
+        rec_lo = 0 if use_aa else rec_aa
+        rec_h[rec_lo:rec_end].copy_(rec_d[rec_lo:rec_end], non_blocking=True)
+        if step_link == 2:
+            ev_rec.record()
         if use_aa:
-            aa_rm_h.copy_(aa_rm.view(-1), non_blocking=True)
             aa_used[aa_idx] = bf.delta[aa_idx]       # the rounded directions the step uses
+        if step_link == 2:
+            # the full-step link alone, behind the read-back: the host waits for the record
+            # only, and the link runs while it reads the verdicts
+            _lib.call("sglm_loss_trials_link", fam, power, n, ld, na, _p(act_d), _p(bf.eta),
+                      _p(bf.deta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), None, 0,
+                      None, None, _p(undo), _p(rp_buf), pad_to(na, 32), None, st)
         if dev_dec:
             up.batch()
             prev_d = up(prev_rel[act], np.float64)
@@ -2440,7 +2488,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             nit_d = up(n_iter[act], np.int32)
             mit_d = up(max_iter[act], np.int32)
             up.flush()
-            _lib.call("sglm_step_decide", na, _p(act_d), _p(Ltr), _p(sc), nts, _p(ts_all),
+            _lib.call("sglm_step_decide", na, _p(act_d), _p(Lrec), _p(sc), nts, _p(ts_all),
                       ARMIJO_SIGMA, float(tol), STOP_SCALE_FLOOR, int(STOP_LEGACY),
                       _p(aa_rm) if use_aa else None, _p(prev_d), _p(fresh_d), _p(nit_d),
                       _p(mit_d), _p(dec64[0]), _p(dec32), _p(dec64[1]), _p(dec64[2]), _p(deci),
@@ -2459,15 +2507,18 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         t_sync = time.perf_counter()
         if dev_dec:
             ev_dec.synchronize()                 # the iteration's round trip (not the link)
+        elif step_link == 2:
+            ev_rec.synchronize()
         else:
             torch.cuda.current_stream().synchronize()          # the iteration's round trip
         if stats is not None:
             stats.sync_wait_s += time.perf_counter() - t_sync
             stats.roundtrips += 1
         up.synced()
-        L = L_h[: na * 5].numpy().reshape(na, 5).copy()
-        dmaxeta = dmax_h[:na].numpy().astype(np.float64)
-        scn = sc_h.numpy().reshape(na, -1).copy()
+        rec_n = rec_h.numpy()
+        L = rec_n[rec_aa:rec_sc].view(np.float64).reshape(na, 5).copy()
+        dmaxeta = rec_n[rec_dm:rec_end].view(np.float32).astype(np.float64)
+        scn = rec_n[rec_sc:rec_dm].view(np.float64).reshape(na, -1).copy()
         gdir, A_, B_, C_, maxd = scn[:, 0], scn[:, 1], scn[:, 2], scn[:, 3], scn[:, 4]
         maxb = scn[:, 5:5 + nts]                # max|w_j + t d_j| (j < p) for t in TS_ALL
         maxdi = scn[:, 5 + nts]                 # |d| of the intercept
@@ -2494,6 +2545,18 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             hit = ok[np.arange(na), first]
             step_a[hit] = ts[1:][first[hit]]
             tix[hit] = 1 + first[hit]
+        full = None
+        if step_link:
+            # the trial-loss pass took the full step for every fit: the others get their old
+            # predictor back (before the second round reads it) and go on as without the pass
+            full = hit & (step_a == 1.0)
+            back = np.flatnonzero(~full)
+            if back.size:
+                bk = up(np.concatenate([act[back], back]), np.int64)
+                bf.eta[bk[:back.size], :n] = undo[bk[back.size:], :n]
+            if stats is not None:
+                stats.step_link += int(full.sum())
+                stats.step_restored += int(back.size)
         more = np.flatnonzero(~hit)                         # positions in act
         if more.size:
             sub_d = up(act[more], np.int32)
@@ -2536,7 +2599,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         if use_aa:
             # a secant-corrected step can be small while the raw Newton step is not
             # (cancellation in f - gamma (dbeta + df)): such a fit is not converged
-            rm = aa_rm_h.numpy().reshape(B0, 2)[act].astype(np.float64)
+            rm = rec_n[:rec_aa].view(np.float32).reshape(B0, 2)[act].astype(np.float64)
             rawp = np.maximum(rm[:, 0] / scale, rm[:, 1])
             relv = np.maximum(relv, rawp)
         stepa = step_a
@@ -2598,6 +2661,45 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             up.flush()
             grad_d, grad_n, grad_bp = deci[3 * B0:], int(di[4 * B0]), pad_to(na, 32)
             dev_linked = True
+        elif step_link:
+            # the fits that took the full step hold their new predictor, and those that go on
+            # their packed R at their row of this list.  The others (put back above) step and
+            # link as before, at their row.  The next gradient reads the rows in this list's
+            # order, stopped fits' rows carried (their gradient rows are never read), as long
+            # as that costs no 32-fit group more than the continuing fits need -- its cost and
+            # its row slabs (hence its bits) depend on the group count alone; continuing fits
+            # beyond those groups are re-linked into rows that stopped fits freed
+            part = ~full
+            done = np.flatnonzero(~cont & part & (step_a != 0.0))
+            if done.size:
+                done_d, tdone_d = up(act[done], np.int32), up(step_a[done], np.float32)
+            if nxt.size:
+                pos = np.arange(na)
+                ngrp = pad_to(int(nxt.size), 32)
+                hi = np.flatnonzero(cont & (pos >= ngrp))
+                rpos, lst = pos.copy(), act.copy()
+                if hi.size:
+                    holes = np.flatnonzero(~cont[:ngrp])[:hi.size]
+                    rpos[hi] = holes
+                    lst[holes] = act[hi]
+                span = int(rpos[cont].max()) + 1
+                rl = np.flatnonzero(cont & (part | (rpos != pos)))
+                if rl.size:
+                    rl_i = up(np.stack([act[rl], rpos[rl]]), np.int32)
+                    rl_t = up(np.where(part[rl], step_a[rl], 0.0), np.float32)
+                linked = up(nxt, np.int32)
+                carried = (up(lst[:span], np.int32), span, pad_to(na, 32))
+            up.flush()
+            _lib.call("sglm_step_update", P, na, _p(act_d), _p(step_d), _p(bf.delta),
+                      _p(beta64_d), st)
+            if done.size:
+                _lib.call("sglm_eta_axpy", n, ld, int(done.size), _p(done_d), _p(tdone_d),
+                          _p(bf.deta), _p(bf.eta), st)
+            if nxt.size and rl.size:
+                _lib.call("sglm_link_update_rp", fam, power, n, ld, int(rl.size), _p(rl_i[0]),
+                          _p(bf.eta), _p(prob.Y), _p(prob.M), _p(fit_resp), _p(fit_mask), None,
+                          None, _p(rp_buf), pad_to(na, 32), _p(rl_i[1]), _p(rl_t), _p(bf.deta),
+                          st)
         elif fused and nxt.size:
             done = np.flatnonzero(~cont & (step_a != 0.0))
             if done.size:
@@ -2625,6 +2727,25 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             drift[act] += step_a * dmaxeta            # max_i |t d_eta_i| over the fit's rows
         fresh_start[act[step_a != 0.0]] = False
         aa_t[act] = step_a
+        # a failed line search on a kept (stale) factor, or on a Hessian shared from a lambda
+        # neighbour, is not a verdict: the next iteration forms a fresh Hessian of the fit's
+        # own instead of stopping it
+        if not const_hess:
+            drift[act[ls_fail & ~fresh]] = np.inf
+            no_share[act[ls_fail & gram_now[act] & ~exact_h[act]]] = True
+            # a fit whose step on the representative's factor failed, or contracted slowly,
+            # forms its own Hessians from here on
+            was_alias = alias[act] >= 0
+            slow = was_alias & (relv > XMASK_SLOW * prev_rel[act]) & (relv > tol)
+            drop = was_alias & (ls_fail | slow)
+            no_alias[act[drop]] = True
+            if stats is not None:
+                stats.stops["alias_dropped"] += int(np.sum(drop))
+        if not const_hess and nxt.size:
+            # the next iteration's Hessian decisions and their distances, enqueued behind
+            # this iteration's predictor update (read back without a stall next iteration) and
+            # ahead of the host's statistics: the GPU has nothing else queued meanwhile
+            plan = hess_plan(nxt)
         if stats is not None:
             stats.newton_iters += 1
             stats.fit_iters += na
@@ -2640,20 +2761,6 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             stats.alg_flop_dense += rest + float(np.sum(np.where(gram_comp[act],
                                                                  nr * pa * (pa + 1), 0.0)))
             stats.gram_fit_iters += int(np.sum(gram_comp[act]))
-        # a failed line search on a kept (stale) factor, or on a Hessian shared from a lambda
-        # neighbour, is not a verdict: the next iteration forms a fresh Hessian of the fit's
-        # own instead of stopping it
-        if not const_hess:
-            drift[act[ls_fail & ~fresh]] = np.inf
-            no_share[act[ls_fail & gram_now[act] & ~exact_h[act]]] = True
-            # a fit whose step on the representative's factor failed, or contracted slowly,
-            # forms its own Hessians from here on
-            was_alias = alias[act] >= 0
-            slow = was_alias & (relv > XMASK_SLOW * prev_rel[act]) & (relv > tol)
-            drop = was_alias & (ls_fail | slow)
-            no_alias[act[drop]] = True
-            if stats is not None:
-                stats.stops["alias_dropped"] += int(np.sum(drop))
         active[act[stop]] = False
         converged[act[stop]] = conv_now[stop]
         active[act[out_of_iters]] = False
@@ -2674,10 +2781,6 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
             stats.stops["line_search_failed"] += int(np.sum(stop_fail & (prop > tol)))
             stats.stops["max_iter"] += int(np.sum(out_of_iters))
             stats.stops["stale_factor_retry"] += int(np.sum(ls_fail & ~fresh))
-        if not const_hess and nxt.size:
-            # the next iteration's Hessian decisions and their distances, enqueued behind
-            # this iteration's predictor update (read back without a stall next iteration)
-            plan = hess_plan(nxt)
         t0 = tick("it_update", t0)
 
     if pending_inv is not None:              # a deferred inversion still reads bf.H / fact_fits
