@@ -712,6 +712,29 @@ int sglm_lag_xtr(const int32_t* occ, const int32_t* tbeg, const int32_t* tend,
                  int64_t n, int32_t P, const float* R, int64_t ld, const int32_t* slots,
                  int32_t nact, double* g, void* work, sglm_stream_t stream);
 
+/* The same gradient from the packed R rows (the contract of sglm_xtr_bits_packed_bp: Rp =
+ * [3][Bp][ld] bf16 pieces, launch rows 0..B-1, G[slots[q]][0..P) float64, padding columns zero,
+ * the ones column the plain sum of R), walked over the occurrences at LDS rate.  The shifts
+ * must be the contiguous range smin..smax in any order: lagpos[j] = the lag index b with
+ * shifts[b] = smin + j.  Rows are cut into tiles of U owned rows with H halo rows in front
+ * (tile i stages design rows [i U - H, (i + 1) U), zeros outside [0, n)); an occurrence u
+ * belongs to the tile that holds v = u - row0 + smin in [i U - H, (i + 1) U - H), and
+ * toff[i][a] (int32 [ntiles + 1][m]) = the index in occ of event a's first occurrence with
+ * v >= i U - H.  sglm_lag_xtr_plan (host only): out[0..7) = U, H, ntiles, the number of row
+ * ranges, tiles per range (both functions of n and ceil(count / 32) alone), the work bytes
+ * for any call with at most `count` fits, and the partial-sum bytes of one (row range, 16-fit
+ * group) that they are made of.  sglm_lag_xtr_packed_ok: 1 where the shape is covered
+ * (m <= 64, K <= 40, contiguous shifts); an uncovered shape returns SGLM_EINVAL.  wg_per_cu:
+ * 1 = one workgroup per CU (leaves LDS and wave slots to a kernel on another stream), else 2. */
+int32_t sglm_lag_xtr_packed_ok(int32_t m, int32_t K, int32_t smin, int32_t smax);
+int sglm_lag_xtr_plan(int64_t n, int32_t count, int32_t K, int32_t P, int64_t* out);
+int sglm_lag_xtr_packed_bp(const int32_t* occ, int32_t nocc, const int32_t* toff,
+                           const int32_t* lagpos, int32_t m, int32_t K, int32_t smin,
+                           int32_t smax, int32_t layout, int64_t row0, int64_t n, int64_t ld,
+                           int32_t P, const void* Rp, int32_t B, int32_t Bp,
+                           const int32_t* slots, double* G, void* work, int32_t wg_per_cu,
+                           sglm_stream_t stream);
+
 /* sglm_xtr_prefer(1): this thread's following sglm_xtr_bits / _packed calls use the
  * one-fit-group four-panel gradient kernel (fewer registers per lane, so work on another
  * stream -- the factorisation chain -- can share the SIMDs); -1 restores the automatic choice. */

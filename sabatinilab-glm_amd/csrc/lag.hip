@@ -305,3 +305,410 @@ extern "C" int sglm_lag_xtr(const int32_t* occ, const int32_t* tbeg, const int32
                         s>>>(part, pl.nranges, nact, P, m * K + 1, slots, g);
     return check_launch("lag_reduce_kernel");
 }
+
+// ---- the occurrence walk at LDS rate on the packed R (sglm_lag_xtr_packed_bp) ---------------
+// The same sum as lag_xtr_kernel, g[(b, a)] = sum over occurrences u of R[u - row0 + s_b], read
+// from the packed three-piece R rows the link writes (no f32 rows needed) and laid out so that
+// the inner loop is one wave-uniform occurrence -> K/4 ds_read_b32 + K/4 f32 adds per lane:
+//   * a workgroup (4 waves) owns 16 fits and a range of row tiles.  A tile is kPxU design rows
+//     plus a halo of H rows in front (H >= K, a multiple of 8), staged in LDS as [row][fit] f32
+//     ((hi + mid) + lo, exactly the f32 the link split); rows outside [0, n) are zeros;
+//   * the shifts are a contiguous range smin..smax, so an occurrence's window is K consecutive
+//     design rows from v = u - row0 + smin.  The occurrence belongs to the tile whose staged
+//     rows start at or before v and whose next tile starts after it (tile i: v in
+//     [i U - H, (i + 1) U - H)): the whole window lies in the staged rows, so the inner loop has
+//     no per-lane bounds test;
+//   * lane = (fit f = lane & 15, phase q = lane >> 4) takes sorted lags j = q + 4 i: one
+//     ds_read_b32 of the wave reads rows v + 4 i .. + 3 of all 16 fits = 64 consecutive words,
+//     64 distinct banks.  Wave w owns events a = w + 4 e; the f32 accumulators [e][i] stay in
+//     registers across the whole row range (statically unrolled);
+//   * the staging store transposes (a thread holds 8 consecutive rows of one fit): lane group
+//     g = lane >> 4 stores its element k ^ g in step k, so the four groups of a wave hit four
+//     different rows mod 4 -- again 64 distinct banks;
+//   * the occurrence indices are wave-uniform: a tile's [event] offsets are one coalesced load
+//     (prefetched a tile ahead), the first 64 occurrences of every event of the wave are
+//     loaded lane-parallel before the staging and broadcast with v_readlane.
+// Range partials go to `work` (f32, the accumulators themselves; the intercept's in float64)
+// and px_reduce_kernel sums them in float64 in a fixed order.
+namespace sglm {
+namespace {
+
+constexpr int kPxT = 256;          // threads per workgroup
+constexpr int kPxU = 1024;         // owned design rows per tile
+constexpr int kPxF = 16;           // fits per workgroup
+constexpr int kPxMaxM = 64;        // events: one lane of the offset load each
+constexpr int kPxMaxK = 40;        // lags: 4 phases x 10 accumulators per event
+constexpr int kPxWgTarget = 512;   // workgroups aimed at: two per CU
+constexpr int kPxPadBlocks = 64;   // blocks of the reduction that zero the padding columns
+// bytes of one (row range, 16-fit group) of partials at the largest instantiation: 4 waves x 16
+// events x NI lags x 64 lanes f32, and 16 float64 intercepts
+constexpr size_t px_group_bytes(int ni) { return (size_t)4 * 16 * ni * 64 * 4 + kPxF * 8; }
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct PxArgs {
+    const int32_t* occ;            // raw occurrence rows, event-major, ascending per event
+    const int32_t* toff;           // [ntiles + 1][m]: first occurrence of event a owned by tile i
+    const int32_t* lagpos;         // [K]: lag index b of sorted position j (shifts[b] = smin + j)
+    int32_t nocc, m, K, layout, P, H;
+    int32_t voff;                  // design row of an occurrence's first lag = u + voff
+    int32_t ntiles, tiles_per;
+    int64_t n, ld;
+};
+
+__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+
+template <int ME, int NI, int UN>
+__global__ void __launch_bounds__(kPxT)
+lag_xtr_packed_kernel(PxArgs a, const uint16_t* __restrict__ Rp, int64_t plane, int32_t count,
+                      float* __restrict__ part, double* __restrict__ partI) {
+    static_assert(NI % 2 == 0, "accumulators are paired");
+    extern __shared__ __attribute__((aligned(16))) char px_lds[];
+    float* L = reinterpret_cast<float*>(px_lds);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int range = blockIdx.x, grp = blockIdx.y;
+    const int tile0 = range * a.tiles_per;
+    const int tile1 = min(tile0 + a.tiles_per, a.ntiles);
+    const int nch = (kPxU + a.H) >> 3;             // 8-row chunks staged per tile
+    const int hch = a.H >> 3;                      // of which halo (counted by the tile before)
+    // staging: this thread's fit (256 % 16 == 0: one fit per thread) and lane group
+    const int sf = tid & 15, sg = (tid >> 4) & 3;
+    const bool son = grp * kPxF + sf < count;
+    const uint16_t* rrow = Rp + (int64_t)(grp * kPxF + sf) * a.ld;
+    double accI = 0.0;                             // intercept: plain sum of the owned rows
+    f32x2 acc[ME][NI / 2];
+#pragma unroll
+    for (int e = 0; e < ME; ++e)
+#pragma unroll
+        for (int i = 0; i < NI / 2; ++i) acc[e][i] = (f32x2){0.0f, 0.0f};
+    int32_t nxt = 0, cur_b = 0;
+    if (lane < a.m) {
+        cur_b = a.toff[(int64_t)tile0 * a.m + lane];
+        nxt = a.toff[(int64_t)(tile0 + 1) * a.m + lane];
+    }
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int32_t tb = cur_b, te = nxt;
+        cur_b = te;
+        if (tile + 1 < tile1 && lane < a.m) nxt = a.toff[(int64_t)(tile + 2) * a.m + lane];
+        // the first 64 occurrences of each of the wave's events (lands during the staging)
+        int32_t ov[ME];
+#pragma unroll
+        for (int e = 0; e < ME; ++e) {
+            const int ae = w + 4 * e;
+            ov[e] = 0;
+            if (ae < a.m) {
+                const int b0 = __builtin_amdgcn_readlane(tb, ae);
+                const int c0 = __builtin_amdgcn_readlane(te, ae) - b0;
+                if (lane < c0 && b0 >= 0 && b0 + lane < a.nocc) ov[e] = a.occ[b0 + lane];
+            }
+        }
+        const int t0 = tile * kPxU - a.H;          // design row of staged row 0
+        __syncthreads();                           // the previous tile's reads are done
+        for (int cb = tid >> 4; cb < nch; cb += 48) {
+            u32x4 hi[3], mi[3], lo[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                const int c = cb + 16 * x;
+                const int64_t t = (int64_t)t0 + 8 * c;
+                hi[x] = mi[x] = lo[x] = (u32x4){0u, 0u, 0u, 0u};
+                if (son && c < nch && t >= 0 && t < a.n) {
+                    const uint16_t* p = rrow + t;
+                    hi[x] = *reinterpret_cast<const u32x4*>(p);
+                    mi[x] = *reinterpret_cast<const u32x4*>(p + plane);
+                    lo[x] = *reinterpret_cast<const u32x4*>(p + 2 * plane);
+                }
+            }
+#pragma unroll
+            for (int x = 0; x < 3; ++x) {
+                const int c = cb + 16 * x;
+                if (c >= nch) break;
+                const int64_t t = (int64_t)t0 + 8 * c;
+                float v[8];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    v[2 * k] = (bf_lo(hi[x][k]) + bf_lo(mi[x][k])) + bf_lo(lo[x][k]);
+                    v[2 * k + 1] = (bf_hi(hi[x][k]) + bf_hi(mi[x][k])) + bf_hi(lo[x][k]);
+                }
+                if (t + 8 > a.n) {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] = t + k < a.n ? v[k] : 0.0f;
+                }
+                if (c >= hch)
+                    accI += (((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3])) +
+                            (((double)v[4] + (double)v[5]) + ((double)v[6] + (double)v[7]));
+                // element k ^ sg in step k (two conditional swap stages)
+                float s1[8], s2[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s1[k] = (sg & 1) ? v[k ^ 1] : v[k];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s2[k] = (sg & 2) ? s1[k ^ 2] : s1[k];
+                float* dst = L + c * (8 * kPxF) + sf;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) dst[(k ^ sg) * kPxF] = s2[k];
+            }
+        }
+        __syncthreads();
+        const int uoff = a.voff - t0;              // staged row of the first lag: u + uoff
+        const float* Ll = L + lane;
+#pragma unroll
+        for (int e = 0; e < ME; ++e) {
+            const int ae = w + 4 * e;
+            if (ae >= a.m) continue;
+            const int b0 = __builtin_amdgcn_readlane(tb, ae);
+            const int c0 = __builtin_amdgcn_readlane(te, ae) - b0;
+            int32_t cur = ov[e];
+            for (int base = 0; base < c0; base += 64) {
+                const int nn = min(64, c0 - base);
+                if (base) {
+                    cur = 0;
+                    if (lane < nn && b0 >= 0 && b0 + base + lane < a.nocc)
+                        cur = a.occ[b0 + base + lane];
+                }
+                int z = 0;
+                for (; z + UN <= nn; z += UN) {
+                    float r[UN][NI];
+#pragma unroll
+                    for (int y = 0; y < UN; ++y) {
+                        int u = __builtin_amdgcn_readlane(cur, z + y) + uoff;
+                        u = min(max(u, 0), kPxU - 1);
+                        const float* p = Ll + u * kPxF;
+#pragma unroll
+                        for (int i = 0; i < NI; ++i) r[y][i] = p[i * (4 * kPxF)];
+                    }
+#pragma unroll
+                    for (int y = 0; y < UN; ++y)
+#pragma unroll
+                        for (int i = 0; i < NI / 2; ++i)
+                            acc[e][i] += (f32x2){r[y][2 * i], r[y][2 * i + 1]};
+                }
+                for (; z < nn; ++z) {
+                    int u = __builtin_amdgcn_readlane(cur, z) + uoff;
+                    u = min(max(u, 0), kPxU - 1);
+                    const float* p = Ll + u * kPxF;
+                    float r[NI];
+#pragma unroll
+                    for (int i = 0; i < NI; ++i) r[i] = p[i * (4 * kPxF)];
+#pragma unroll
+                    for (int i = 0; i < NI / 2; ++i) acc[e][i] += (f32x2){r[2 * i], r[2 * i + 1]};
+                }
+            }
+        }
+    }
+    // the range's partial sums, in the accumulators' own order [wave][e][i][lane] (every store
+    // of a wave is 64 consecutive floats; px_reduce_kernel maps them to columns): f32, exactly
+    // the accumulators.  Measured with float64 partials by (fit, column), 8-byte stores 16 KB
+    // apart: 0.21 ms per call at 6 fits, against an LDS floor of 0.012 ms
+    {
+        const int ngrp = gridDim.y;
+        float* out = part + ((((int64_t)range * ngrp + grp) * 4 + w) * ME) * (NI * 64) + lane;
+#pragma unroll
+        for (int e = 0; e < ME; ++e)
+#pragma unroll
+            for (int i = 0; i < NI; ++i) out[(e * NI + i) * 64] = acc[e][i / 2][i & 1];
+    }
+    __syncthreads();                               // LDS reused for the intercept sums
+    double* red = reinterpret_cast<double*>(px_lds);
+    red[tid] = accI;
+    __syncthreads();
+    if (tid < kPxF) {
+        double I = 0.0;
+        for (int k = 0; k < kPxT / kPxF; ++k) I += red[tid + kPxF * k];
+        partI[((int64_t)range * gridDim.y + grp) * kPxF + tid] = I;
+    }
+}
+
+// g[slots[fit]][c] = the sum over the ranges of the partials, in a fixed order: a block sums 64
+// consecutive accumulators (or 64 intercepts) in four range segments, seg 0..3 added in that
+// order; the last blocks zero the padding columns
+template <int ME, int NI>
+__global__ void __launch_bounds__(256)
+px_reduce_kernel(const float* __restrict__ part, const double* __restrict__ partI, int32_t nranges,
+                 int32_t ngrp, int32_t count, int32_t m, int32_t K, int32_t layout, int32_t P,
+                 const int32_t* __restrict__ lagpos, const int32_t* __restrict__ slots,
+                 double* __restrict__ g) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x, lane = tid & 63, seg = tid >> 6;
+    const int64_t nmain = (int64_t)ngrp * 4 * ME * NI;          // blocks of 64 accumulators
+    const int64_t nint = ((int64_t)ngrp * kPxF + 63) / 64;      // blocks of 64 intercepts
+    const int64_t blk = blockIdx.x;
+    const int r0 = (int)((int64_t)nranges * seg / 4), r1 = (int)((int64_t)nranges * (seg + 1) / 4);
+    if (blk < nmain + nint) {
+        const bool main_ = blk < nmain;
+        const int64_t t = main_ ? blk * 64 + lane : (blk - nmain) * 64 + lane;
+        const int64_t stride = main_ ? nmain * 64 : (int64_t)ngrp * kPxF;
+        const bool live = main_ || t < stride;
+        double s0 = 0.0, s1 = 0.0;
+        if (live) {
+            int r = r0;
+            if (main_) {
+                for (; r + 2 <= r1; r += 2) {
+                    s0 += (double)part[r * stride + t];
+                    s1 += (double)part[(r + 1) * stride + t];
+                }
+                if (r < r1) s0 += (double)part[r * stride + t];
+            } else {
+                for (; r + 2 <= r1; r += 2) {
+                    s0 += partI[r * stride + t];
+                    s1 += partI[(r + 1) * stride + t];
+                }
+                if (r < r1) s0 += partI[r * stride + t];
+            }
+        }
+        red[tid] = s0 + s1;
+        __syncthreads();
+        if (seg == 0 && live) {
+            const double v = ((red[lane] + red[64 + lane]) + red[128 + lane]) + red[192 + lane];
+            if (main_) {
+                int64_t x = blk;
+                const int i = (int)(x % NI); x /= NI;
+                const int e = (int)(x % ME); x /= ME;
+                const int w = (int)(x & 3), grp = (int)(x >> 2);
+                const int fit = grp * kPxF + (lane & 15), j = (lane >> 4) + 4 * i, ae = w + 4 * e;
+                if (fit < count && j < K && ae < m) {
+                    const int b = lagpos[j];
+                    g[(int64_t)slots[fit] * P + (layout ? ae * K + b : b * m + ae)] = v;
+                }
+            } else if (t < count) {
+                g[(int64_t)slots[t] * P + (int64_t)m * K] = v;
+            }
+        }
+        return;
+    }
+    const int pad = P - (m * K + 1);
+    const int64_t len = (int64_t)count * pad;
+    for (int64_t x = (blk - nmain - nint) * 256 + tid; x < len; x += (int64_t)kPxPadBlocks * 256)
+        g[(int64_t)slots[x / pad] * P + (m * K + 1) + x % pad] = 0.0;
+}
+
+struct PxPlan {
+    int H, me, ni;                                 // halo rows; the instantiation's tiers
+    int64_t ntiles, nranges, tiles_per;
+};
+
+bool px_shape_ok(int32_t m, int32_t K, int32_t smin, int32_t smax) {
+    return m >= 1 && m <= kPxMaxM && K >= 1 && K <= kPxMaxK && (int64_t)smax - smin + 1 == K;
+}
+
+// Row ranges: a function of (n, ceil(count / 32)) alone, so a fit's bits depend on the number of
+// 32-fit groups only (the engine's carried-row rule assumes the same of the dense kernel)
+PxPlan px_plan(int64_t n, int32_t count, int32_t K) {
+    PxPlan p;
+    p.ni = K <= 8 ? 2 : 10;
+    p.me = 0;
+    p.H = (4 * p.ni + 7) / 8 * 8;
+    p.ntiles = (n + p.H + kPxU - 1) / kPxU;
+    const int64_t g32 = ((int64_t)count + 31) / 32;
+    int64_t nr = kPxWgTarget / (2 * g32);
+    if (nr > p.ntiles) nr = p.ntiles;
+    if (nr < 1) nr = 1;
+    p.tiles_per = (p.ntiles + nr - 1) / nr;
+    p.nranges = (p.ntiles + p.tiles_per - 1) / p.tiles_per;
+    return p;
+}
+
+size_t px_work_bytes(int64_t n, int32_t count, int32_t K, int32_t P) {
+    size_t mx = 0;                                 // any call with at most `count` fits
+    for (int32_t b = 1; b <= count; ++b) {
+        const PxPlan pl = px_plan(n, b, K);
+        const size_t wbytes = (size_t)pl.nranges * ((b + kPxF - 1) / kPxF) * px_group_bytes(pl.ni);
+        mx = wbytes > mx ? wbytes : mx;
+    }
+    return mx;
+}
+
+template <int ME, int NI>
+int px_launch(const PxArgs& a, const PxPlan& pl, const uint16_t* Rp, int64_t plane, int32_t count,
+              void* work, size_t lds, const int32_t* slots, double* G, hipStream_t s) {
+    auto* kern = &lag_xtr_packed_kernel<ME, NI, (NI > 2 ? 2 : 4)>;
+    static bool attr = false;                      // > 64 KB of dynamic LDS (gfx950: 160 KB)
+    if (!attr) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kPxF * (kPxU + 40) * 4 * 2) != hipSuccess) {
+            set_error("lag_xtr_packed_kernel: dynamic LDS refused");
+            return SGLM_EHIP;
+        }
+        attr = true;
+    }
+    const int ngrp = (count + kPxF - 1) / kPxF;
+    float* part = reinterpret_cast<float*>(work);
+    double* partI = reinterpret_cast<double*>(
+        reinterpret_cast<char*>(work) + (size_t)pl.nranges * ngrp * 4 * ME * NI * 64 * sizeof(float));
+    dim3 grid((unsigned)pl.nranges, (unsigned)ngrp);
+    kern<<<grid, kPxT, lds, s>>>(a, Rp, plane, count, part, partI);
+    int st = check_launch("lag_xtr_packed_kernel");
+    if (st) return st;
+    const int64_t blocks = (int64_t)ngrp * 4 * ME * NI + ((int64_t)ngrp * kPxF + 63) / 64 +
+                           (a.P > a.m * a.K + 1 ? kPxPadBlocks : 0);
+    px_reduce_kernel<ME, NI><<<(unsigned)blocks, 256, 0, s>>>(
+        part, partI, (int32_t)pl.nranges, ngrp, count, a.m, a.K, a.layout, a.P, a.lagpos, slots, G);
+    return check_launch("px_reduce_kernel");
+}
+
+}  // namespace
+}  // namespace sglm
+
+extern "C" int32_t sglm_lag_xtr_packed_ok(int32_t m, int32_t K, int32_t smin, int32_t smax) {
+    return px_shape_ok(m, K, smin, smax) ? 1 : 0;
+}
+
+extern "C" int sglm_lag_xtr_plan(int64_t n, int32_t count, int32_t K, int32_t P, int64_t* out) {
+    if (!out || n <= 0 || count < 1 || K < 1 || K > kPxMaxK || P < 1 ||
+        n > ((int64_t)1 << 31) - 4 * kPxU) {
+        set_error("sglm_lag_xtr_plan: bad args (n=%lld, count=%d, K=%d <= %d)", (long long)n,
+                  count, K, kPxMaxK);
+        return SGLM_EINVAL;
+    }
+    const PxPlan pl = px_plan(n, count, K);
+    out[0] = kPxU;
+    out[1] = pl.H;
+    out[2] = pl.ntiles;
+    out[3] = pl.nranges;
+    out[4] = pl.tiles_per;
+    out[5] = (int64_t)px_work_bytes(n, count, K, P);
+    out[6] = (int64_t)px_group_bytes(pl.ni);
+    return SGLM_OK;
+}
+
+extern "C" int sglm_lag_xtr_packed_bp(const int32_t* occ, int32_t nocc, const int32_t* toff,
+                                      const int32_t* lagpos, int32_t m, int32_t K, int32_t smin,
+                                      int32_t smax, int32_t layout, int64_t row0, int64_t n,
+                                      int64_t ld, int32_t P, const void* Rp, int32_t B,
+                                      int32_t Bp, const int32_t* slots, double* G, void* work,
+                                      int32_t wg_per_cu, sglm_stream_t stream) {
+    if (B <= 0) return SGLM_OK;
+    if (!px_shape_ok(m, K, smin, smax)) {
+        set_error("sglm_lag_xtr_packed_bp: shape not covered (m=%d <= %d, K=%d <= %d, shifts "
+                  "%d..%d contiguous)", m, kPxMaxM, K, kPxMaxK, smin, smax);
+        return SGLM_EINVAL;
+    }
+    if (!occ || !toff || !lagpos || !Rp || !slots || !G || !work || nocc < 0 || n <= 0 ||
+        n > ld || ld % 8 || (int64_t)m * K + 1 > P || Bp < B ||
+        n > ((int64_t)1 << 31) - 4 * kPxU || row0 - smin > ((int64_t)1 << 30) ||
+        smin - row0 > ((int64_t)1 << 30)) {
+        set_error("sglm_lag_xtr_packed_bp: bad args");
+        return SGLM_EINVAL;
+    }
+    const PxPlan pl = px_plan(n, B, K);
+    PxArgs a;
+    a.occ = occ; a.toff = toff; a.lagpos = lagpos; a.nocc = nocc;
+    a.m = m; a.K = K; a.layout = layout; a.P = P; a.H = pl.H;
+    a.voff = (int32_t)(smin - row0);
+    a.ntiles = (int32_t)pl.ntiles; a.tiles_per = (int32_t)pl.tiles_per;
+    a.n = n; a.ld = ld;
+    hipStream_t s = as_stream(stream);
+    // one workgroup per CU on request (beside a factorisation chain): LDS padded past half a CU's
+    size_t lds = (size_t)kPxF * (kPxU + pl.H) * sizeof(float);
+    if (wg_per_cu == 1) lds = (size_t)kPxF * (kPxU + 40) * sizeof(float) * 2;
+    const uint16_t* rp = reinterpret_cast<const uint16_t*>(Rp);
+    const int64_t plane = (int64_t)Bp * ld;
+    const int me = (m + 3) / 4;
+    if (pl.ni == 2)
+        return me <= 4 ? px_launch<4, 2>(a, pl, rp, plane, B, work, lds, slots, G, s)
+                       : px_launch<16, 2>(a, pl, rp, plane, B, work, lds, slots, G, s);
+    return me <= 4    ? px_launch<4, 10>(a, pl, rp, plane, B, work, lds, slots, G, s)
+           : me <= 13 ? px_launch<13, 10>(a, pl, rp, plane, B, work, lds, slots, G, s)
+                      : px_launch<16, 10>(a, pl, rp, plane, B, work, lds, slots, G, s);
+}

@@ -150,6 +150,11 @@ SIGNATURES = {
     "sglm_mixed_to_h": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sglm_lag_xtr": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i32, _vp, _i64,
                                _vp, _i32, _vp, _vp, _vp]),
+    "sglm_lag_xtr_packed_ok": (_i32, [_i32, _i32, _i32, _i32]),
+    "sglm_lag_xtr_plan": (C.c_int, [_i64, _i32, _i32, _i32, _vp]),
+    "sglm_lag_xtr_packed_bp": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64,
+                                         _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32,
+                                         _vp]),
     "sglm_group_rows_work_bytes": (_sz, [_i64]),
     "sglm_group_rows": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sglm_trial_lookup": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),

@@ -142,6 +142,20 @@ DEFER_INV_MIN = int(__import__("os").environ.get("SGLM_DEFER_INV_MIN", "0"))
 GRAD_FIRST = __import__("os").environ.get("SGLM_GRAD_FIRST", "1") == "1"
 # gradient kernel that co-resides with the factorisation chain in iterations that form factors
 XTR_COCHAIN = __import__("os").environ.get("SGLM_XTR_COCHAIN", "1") == "1"
+# SGLM_XTR_EVENTS: the packed-R gradient of a pure lag design (Design.lag, no continuous
+# columns, not row-sharded, shape covered by sglm_lag_xtr_packed_ok) walked over the event
+# occurrences (sglm_lag_xtr_packed_bp) instead of the dense bit-plane MFMA product.
+# "1": always, "0": never, "auto": per fit count (xtr_events_auto).
+# SGLM_XTR_EVENTS_COWG: workgroups per CU of the walk where a factorisation chain runs beside it.
+XTR_EVENTS = __import__("os").environ.get("SGLM_XTR_EVENTS", "auto")
+XTR_EVENTS_COWG = int(__import__("os").environ.get("SGLM_XTR_EVENTS_COWG", "2"))
+
+
+def xtr_events_auto(count: int) -> bool:
+    """`auto` of SGLM_XTR_EVENTS.  No crossover: on the C4 design (tools/lag_bench.py, one
+    MI355X, ms per call, dense / walk) 6 fits 0.282 / 0.142, 30: 0.321 / 0.194, 47: 0.608 /
+    0.327, 65: 0.842 / 0.476, 78: 0.868 / 0.484, 120: 1.109 / 0.638 -- the walk at every count."""
+    return True
 # constant-weight Grams of lagged event designs from the event cross-correlations
 LAG_GRAM = __import__("os").environ.get("SGLM_LAG_GRAM", "1") == "1"
 # concurrent factorisation chains for a batch of >= CHOL_SPLIT_MIN new factorisations.  Round 3
@@ -972,6 +986,31 @@ def _canonical_lags(cols, shifts, m, event_major):
     return ev, [int(x) for x in sl]
 
 
+def lag_xtr_plan(n: int, count: int, K: int, P: int) -> dict:
+    """sglm_lag_xtr_plan (host only): the tile rows U and halo H, the tile and row-range counts
+    the work bytes of sglm_lag_xtr_packed_bp for up to ``count`` fits and the partial-sum bytes
+    of one (row range, 16-fit group)."""
+    out = np.zeros(7, dtype=np.int64)
+    _lib.call("sglm_lag_xtr_plan", int(n), int(count), int(K), int(P), out.ctypes.data)
+    return dict(zip(("U", "H", "ntiles", "nranges", "tiles_per", "work_bytes", "group_bytes"),
+                    (int(v) for v in out)))
+
+
+def lag_xtr_offsets(ev, rows, m: int, row0: int, smin: int, U: int, H: int, ntiles: int):
+    """The (tile, event) offset table of sglm_lag_xtr_packed_bp, int32 [ntiles + 1][m]: entry
+    [i][a] = the index, in the event-major ascending occurrence list (``ev``, ``rows``: int64
+    tensors), of event a's first occurrence u whose first-lag design row v = u - row0 + smin is
+    >= i U - H.  Tile i owns v in [i U - H, (i + 1) U - H) and stages design rows
+    [i U - H, (i + 1) U), so the K <= H rows of the window lie in it.  Design-level: it depends
+    on the events and the shifts alone."""
+    big = 1 << 40
+    keys = ev.to(torch.int64) * big + rows.to(torch.int64)
+    t0 = torch.arange(ntiles + 1, dtype=torch.int64, device=keys.device) * U - H + row0 - smin
+    a = torch.arange(m, dtype=torch.int64, device=keys.device) * big
+    lo = t0[:, None] + a[None, :]
+    return torch.searchsorted(keys, lo.reshape(-1)).to(torch.int32).contiguous()
+
+
 class LagStructure:
     """A time-shifted 0/1 event design by its events (sglm_lag_xtr): X[t, col(b, a)] =
     E[t + row0 - shifts[b], a].  occ = every event's occurrence rows of E, event-major and
@@ -1019,6 +1058,15 @@ class LagStructure:
         # occurrence bitmap [m][nwords] (bit v & 31 of word v >> 5)
         self.n, self.n_raw = int(n), int(N_raw)
         self.smin, self.smax = int(sh.min()), int(sh.max())
+        # the occurrence walk on the packed R (sglm_lag_xtr_packed_bp), where the shape is
+        # covered: its (tile, event) offset table and the lag index of every sorted shift
+        self.px = None
+        if (_lib.query("sglm_lag_xtr_packed_ok", self.m, self.K, self.smin, self.smax)
+                and int(n) < (1 << 31) - 8192):
+            pl = lag_xtr_plan(int(n), 1, self.K, 1)
+            self.px = (lag_xtr_offsets(ev, rows, self.m, self.row0, self.smin, pl["U"],
+                                       pl["H"], pl["ntiles"]),
+                       torch.from_numpy(np.argsort(sh).astype(np.int32)).to(dev))
         cnt = torch.bincount(ev, minlength=m)
         self.ev_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
                                  torch.cumsum(cnt, 0)]).to(torch.int32).contiguous()
@@ -1395,6 +1443,7 @@ class IrlsStats:
     shared: int = 0             # fit-iterations on a lambda neighbour's Gram (own factor)
     lag_grams: int = 0          # Grams from the event cross-correlations (sglm_lag_gram)
     grad_dedup: int = 0         # fit gradients copied from an identical start (GRAD_DEDUP)
+    grad_events: int = 0        # gradient calls walked over the occurrences (SGLM_XTR_EVENTS)
     rank_grams: int = 0         # exact mask Grams for the rank decisions of unpenalised fits
     chain_host_s: float = 0.0   # host time spent enqueueing the factorisation chains
     aa_fit_iters: int = 0       # fit-iterations whose direction took the secant correction
@@ -2017,6 +2066,12 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     if use_rp:
         rp_buf = _work(3 * pad_to(B0, 32) * ld * 2, dev, "rp")
         gx_work = _work(_lib.query("sglm_xtr_bits_packed_work_bytes", P, B0, ld), dev, "xtr")
+    # the packed-R gradient from the event occurrences (XTR_EVENTS): pure lag designs only
+    ev_px = None
+    if (use_rp and XTR_EVENTS != "0" and d.lag is not None and d.cont is None
+            and d.slab is None and comm is None and getattr(d.lag, "px", None) is not None):
+        ev_px = d.lag.px
+        ev_work = _work(lag_xtr_plan(n, B0, d.lag.K, P)["work_bytes"], dev, "xtrev")
     if use_lag:
         lag_work = _work(_lib.query("sglm_lag_xtr_work_bytes", P, d.lag.K, B0, n), dev, "xtr")
     R_out, Rp_out = (_p(bf.R), None) if use_lag else (None, _p(rp_buf) if use_rp else None)
@@ -2126,14 +2181,25 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 # leaves it room on the SIMDs (sglm_xtr_prefer)
                 cochain = (cochain_ok and XTR_COCHAIN and nref > 0 and SOLVE_INV
                            and CHOL_STREAM != "serial")
-                if cochain:
-                    _lib.call("sglm_xtr_prefer", 1)
-                try:
-                    _lib.call("sglm_xtr_bits_packed_bp", _p(d.cbits_full()), ld, P, n,
-                              _p(rp_buf), grad_n, grad_bp, _p(grad_d), _p(bf.g), _p(gx_work), st)
-                finally:
+                if ev_px is not None and (XTR_EVENTS == "1" or xtr_events_auto(grad_n)):
+                    lg = d.lag
+                    _lib.call("sglm_lag_xtr_packed_bp", _p(lg.occ), int(lg.occ.numel()),
+                              _p(ev_px[0]), _p(ev_px[1]), lg.m, lg.K, lg.smin, lg.smax,
+                              lg.layout, lg.row0, n, ld, P, _p(rp_buf), grad_n, grad_bp,
+                              _p(grad_d), _p(bf.g), _p(ev_work),
+                              XTR_EVENTS_COWG if cochain else 2, st)
+                    if stats is not None:
+                        stats.grad_events += 1
+                else:
                     if cochain:
-                        _lib.call("sglm_xtr_prefer", -1)
+                        _lib.call("sglm_xtr_prefer", 1)
+                    try:
+                        _lib.call("sglm_xtr_bits_packed_bp", _p(d.cbits_full()), ld, P, n,
+                                  _p(rp_buf), grad_n, grad_bp, _p(grad_d), _p(bf.g),
+                                  _p(gx_work), st)
+                    finally:
+                        if cochain:
+                            _lib.call("sglm_xtr_prefer", -1)
                 # a mixed design's continuous coordinates, float64 from the same packed R
                 d.mix_xtr(2, rp_buf, ld, grad_bp, None, grad_d, grad_n, bf.g)
                 if g_copy is not None:
