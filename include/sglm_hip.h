@@ -928,6 +928,51 @@ int sglm_host_group_runs(const int64_t* start, const int64_t* rlen, const int64_
                          int64_t nruns, const uint8_t* side, int32_t nsplits, int64_t G,
                          int64_t* const* out, const int64_t* len, int32_t nthreads);
 
+/* --- Proximal Newton for the elastic-net penalised log-link fits (sglm_hip/pn.py) ----------
+ * Objective per fit in the sum scaling: sum m loss + l1 |w|_1 + l2/2 |w|^2, the intercept
+ * unpenalised.  Launch row f < nfit is fit slot k = slots[f]; H [*][P][P] (f32 upper triangle
+ * of X~^T diag(m loss'') X~, the ones column at index p, as sglm_syrk / sglm_lag_gram_w leave
+ * it), g and beta [*][P] float64 are indexed by slot, everything else by launch row.  icpt[f]
+ * != 0: the fit has an intercept (eliminated from the model when H_pp > 0).
+ *
+ * sglm_pn_model: Q[f] (p x p float64, row-major, bitwise symmetric, written along rows) and
+ *   q[f] (p) of the quadratic model over u = w + delta_w,
+ *   1/2 u^T Q u - q^T u + l1 |u|_1 + l2/2 |u|^2:
+ *   Q = H_xx - h h^T / H_pp, q = Q w - (g_x - h g_p / H_pp) with h = H[0..p)[p], w = beta[k][0..p)
+ *   (Q = H_xx, q = Q w - g_x without an intercept).  q's sums run in a fixed order. */
+int sglm_pn_model(const float* H, int32_t P, int32_t p, const int32_t* slots,
+                  const uint8_t* icpt, int32_t nfit, const double* g, const double* beta,
+                  double* Q, double* q, sglm_stream_t stream);
+/* sglm_enet_cd_warm: cyclic coordinate descent on that model, one Q per fit (Q [nfit][p][p], q,
+ *   l1, l2 per launch row), started from w[f] (in/out, [nfit][p]); p <= 4096.  Schedule: a full
+ *   sweep; sweeps over the coordinates with u_j != 0 (only their rows of Q are read) until
+ *   max|du| <= tol max|u|; a full sweep again; until a full sweep meets the tolerance too, or
+ *   max_sweeps sweeps in all.  Coordinates with Q_jj <= 0 are set to exactly 0; zeros are exact
+ *   0.0.  A start whose first full sweep already meets the tolerance is returned bitwise as it
+ *   came.  sweeps[f] = { full sweeps, restricted sweeps }, nnz[f] = non-zero coordinates. */
+int sglm_enet_cd_warm(const double* Q, int32_t p, int32_t nfit, const double* q, const double* l1,
+                      const double* l2, int32_t max_sweeps, double tol, double* w,
+                      int32_t* sweeps, int32_t* nnz, sglm_stream_t stream);
+/* sglm_pn_step: from the model's minimiser u [nfit][p]: delta[k] (f32 [*][P] by slot) =
+ *   (u - w, delta_b, 0 ...) with delta_b = -(g_p + h^T (u - w)) / H_pp (0 without an
+ *   intercept), and rec[f] (4 + 2 T float64, fixed-order wave-shuffle reductions) =
+ *   { delta_b, the Armijo decrease g.delta + l2 w.delta_w + l1 (|u|_1 - |w|_1),
+ *     the KKT violation of (w, b): max_j v_j, v_j = |g_j + l2 w_j + l1 sign w_j| where w_j != 0,
+ *     max(|g_j + l2 w_j| - l1, 0) elsewhere, and |g_p| with an intercept,
+ *     max_j |u_j - w_j|,
+ *     pen[0..T): l1 sum |w + t delta_w| + l2/2 sum (w + t delta_w)^2 at t = ts[0..T),
+ *     maxb[0..T): max_j |w_j + t delta_w_j| }   (t == 1 evaluates u itself); T <= 16. */
+int sglm_pn_step(const float* H, int32_t P, int32_t p, const int32_t* slots, const uint8_t* icpt,
+                 int32_t nfit, const double* g, const double* beta, const double* u,
+                 const double* l1, const double* l2, const double* ts, int32_t T, float* delta,
+                 double* rec, sglm_stream_t stream);
+/* sglm_pn_update: the step taken, beta[k][0..p) = u[f] where step[f] == 1 (zeros stay exact),
+ *   else w + step[f] (u[f] - w); beta[k][p] += step[f] * rec[f * rec_stride] (delta_b);
+ *   step[f] == 0 leaves the fit as it is. */
+int sglm_pn_update(int32_t P, int32_t p, const int32_t* slots, int32_t nfit, const double* step,
+                   const double* u, const double* rec, int32_t rec_stride, double* beta,
+                   sglm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

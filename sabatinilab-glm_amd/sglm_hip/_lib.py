@@ -187,6 +187,12 @@ SIGNATURES = {
                                      _vp, _vp]),
     "sglm_prep_work_bytes": (_sz, [_i64]),
     "sglm_prep_session": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "sglm_pn_model": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sglm_enet_cd_warm": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.c_double, _vp, _vp,
+                                    _vp, _vp]),
+    "sglm_pn_step": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _i32, _vp, _vp, _vp]),
+    "sglm_pn_update": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
 }
 
 

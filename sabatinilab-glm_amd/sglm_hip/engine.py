@@ -1416,6 +1416,7 @@ class FitReq:
     coef0: Optional[np.ndarray] = None
     intercept0: Optional[float] = None
     drop: int = -1                  # index into the call's drop-set table (< 0: the full model)
+    l1: float = 0.0                 # L1 penalty of the SUM objective (l1 |w|_1; pn.prox_newton)
 
 
 @dataclass
@@ -1451,6 +1452,10 @@ class IrlsStats:
     step_restored: int = 0      # fit-iterations put back from the undo copy of that link
     drop_reduced: int = 0       # drop-set fits solved off the full model's factor (reduced solve)
     drop_excluded: int = 0      # drop-set fits solved on a factor of their own (exclusion route)
+    pn_fit_iters: int = 0       # fit-iterations of the proximal Newton solve (pn.prox_newton)
+    cd_full_sweeps: int = 0     # ... their coordinate-descent sweeps over every coordinate
+    cd_active_sweeps: int = 0   # ... and over the non-zero coordinates only
+    pn_events: list = field(default_factory=list)   # with record: (kernel, start, end) events
     # flop actually executed by the algorithm, summed over fit-iterations: each computed Gram at
     # the count of the kernel that formed it (dense: n p'(p'+1); event-structured: LagStructure
     # flop1; event correlations: their histogram adds), new factors p'^3/3, gradient / eta /

@@ -12,6 +12,8 @@ kwargs), and replace their numerics with the batched IRLS engine:
   TweedieRegressor  mean loss + alpha/2 ||w||^2                -> lam = alpha * n_train
                     (power 0 identity -> squared loss; power >= 1 log link -> Tweedie-log)
   Lasso/ElasticNet  1/(2n)||.||^2 + a rho |w|_1 + a(1-rho)/2 ||w||^2 -> Gram-space CD
+  TweedieRegressor(l1_ratio=rho > 0), log link:
+                    mean loss + a rho |w|_1 + a(1-rho)/2 ||w||^2 -> proximal Newton (pn.py)
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ class NotYetImplementedError(NotImplementedError):
 
 @dataclass
 class Objective:
-    kind: str          # 'irls' | 'cd'
+    kind: str          # 'irls' | 'cd' | 'pn' (log link with an L1 term: pn.prox_newton)
     family: int
     power: float
     alpha: float
@@ -41,6 +43,14 @@ class Objective:
 
     def lam(self, n_train: float) -> float:
         return self.alpha * n_train if self.lam_scale == "n" else self.alpha
+
+    def l1(self, n_train: float) -> float:
+        """L1 penalty of a 'pn' objective in the engine's sum scaling (alpha rho n)."""
+        return self.alpha * self.l1_ratio * n_train
+
+    def l2(self, n_train: float) -> float:
+        """L2 penalty of a 'pn' objective in the engine's sum scaling (alpha (1 - rho) n)."""
+        return self.alpha * (1.0 - self.l1_ratio) * n_train
 
 
 def _check_y_range(power: float, y: np.ndarray):
@@ -214,6 +224,12 @@ class _EngineRegressor:
         if obj.kind == "cd":
             from . import cd
             res = cd.enet_fit(prob, [obj], [0], [0], coef0=[c0])[0]
+        elif obj.kind == "pn":
+            from . import pn
+            nt = X.shape[0]
+            req = E.FitReq(obj.family, obj.power, obj.l2(nt), 0, 0, obj.fit_intercept,
+                           obj.max_iter, c0, b0, l1=obj.l1(nt))
+            (res,), _ = pn.prox_newton(prob, [req])
         else:
             req = E.FitReq(obj.family, obj.power, obj.lam(X.shape[0]), 0, 0, obj.fit_intercept,
                            obj.max_iter, c0, b0)
@@ -322,13 +338,13 @@ class Lasso(ElasticNet):
 
 class TweedieRegressor(_EngineRegressor):
     _params = ("power", "alpha", "fit_intercept", "link", "solver", "max_iter", "tol",
-               "warm_start", "verbose")
+               "warm_start", "verbose", "l1_ratio")
 
     def __init__(self, *, power=0.0, alpha=1.0, fit_intercept=True, link="auto", solver="lbfgs",
-                 max_iter=100, tol=1e-4, warm_start=False, verbose=0):
+                 max_iter=100, tol=1e-4, warm_start=False, verbose=0, l1_ratio=0.0):
         super().__init__(power=power, alpha=alpha, fit_intercept=fit_intercept, link=link,
                          solver=solver, max_iter=max_iter, tol=tol, warm_start=warm_start,
-                         verbose=verbose)
+                         verbose=verbose, l1_ratio=l1_ratio)
 
     def _log_link(self):
         if self.link == "auto":
@@ -352,6 +368,17 @@ class TweedieRegressor(_EngineRegressor):
                                          "is outside the engine's families")
         if self.alpha < 0:
             raise ValueError("alpha must be >= 0")
+        rho = float(self.l1_ratio)
+        if not 0.0 <= rho <= 1.0:
+            raise ValueError(f"The 'l1_ratio' parameter of {type(self).__name__} must be a float "
+                             f"in the range [0.0, 1.0]. Got {self.l1_ratio!r} instead.")
+        if rho > 0.0 and self.alpha > 0:
+            if fam == E.FAM_SQUARED:
+                # power 0 with the identity link is sklearn's ElasticNet objective itself
+                return ElasticNet(alpha=self.alpha, l1_ratio=rho,
+                                  fit_intercept=self.fit_intercept).objective()
+            return Objective("pn", fam, p, float(self.alpha), "n", self.fit_intercept,
+                             int(self.max_iter), rho)
         return Objective("irls", fam, p if fam == E.FAM_TWEEDIE_LOG else 0.0, float(self.alpha),
                          "n", self.fit_intercept, int(self.max_iter))
 
@@ -373,13 +400,14 @@ class TweedieRegressor(_EngineRegressor):
 
 
 class PoissonRegressor(TweedieRegressor):
-    _params = ("alpha", "fit_intercept", "solver", "max_iter", "tol", "warm_start", "verbose")
+    _params = ("alpha", "fit_intercept", "solver", "max_iter", "tol", "warm_start", "verbose",
+               "l1_ratio")
 
     def __init__(self, *, alpha=1.0, fit_intercept=True, solver="lbfgs", max_iter=100, tol=1e-4,
-                 warm_start=False, verbose=0):
+                 warm_start=False, verbose=0, l1_ratio=0.0):
         super().__init__(power=1.0, alpha=alpha, fit_intercept=fit_intercept, link="log",
                          solver=solver, max_iter=max_iter, tol=tol, warm_start=warm_start,
-                         verbose=verbose)
+                         verbose=verbose, l1_ratio=l1_ratio)
 
 
 class LogisticRegression:

@@ -341,6 +341,10 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
         # (Design.from_events / from_host with slab=grid.rank_slab(n)) -- a full Design in a
         # process group is sharded by fits instead
         comm = RowComm(dist)
+    if comm is not None and any(o.kind == "pn" for g in groups for o in g["objectives"]):
+        from .estimators import NotYetImplementedError
+        raise NotYetImplementedError("row-sharded solve of elastic-net log-link objectives "
+                                     "(Poisson / Gamma / Tweedie with l1_ratio > 0)")
     dsets = None
     if drop_sets is not None:
         dsets = check_drop_sets(drop_sets, X.p if isinstance(X, E.Design)
@@ -418,7 +422,8 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
     solve_groups = {}
     for i in mine:
         obj = objective(i)
-        key = ("cd", 0.0) if obj.kind == "cd" else (obj.family, float(obj.power))
+        key = (("cd", 0.0) if obj.kind == "cd" else ("pn", float(obj.power)) if obj.kind == "pn"
+               else (obj.family, float(obj.power)))
         solve_groups.setdefault(key, []).append(i)
     for key, idxs in solve_groups.items():
         reqs = []
@@ -429,10 +434,12 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
             _, _, _, m, r, _ = table[i]
             obj = objective(i)
             cnt = counts[m]
-            reqs.append(E.FitReq(obj.family, obj.power, obj.lam(cnt), local[m], r,
-                                 obj.fit_intercept, obj.max_iter,
+            pn_obj = obj.kind == "pn"
+            reqs.append(E.FitReq(obj.family, obj.power, obj.l2(cnt) if pn_obj else obj.lam(cnt),
+                                 local[m], r, obj.fit_intercept, obj.max_iter,
                                  None if coef0 is None else np.asarray(coef0, float),
-                                 None if intercept0 is None else float(intercept0)))
+                                 None if intercept0 is None else float(intercept0),
+                                 l1=obj.l1(cnt) if pn_obj else 0.0))
             if dsets is not None and dsets[v % nds]:
                 reqs[-1].drop = v % nds
         t0 = tick("fit_table", t0)
@@ -443,6 +450,11 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
             res, eta = cd.enet_batch(prob, [objective(i) for i in idxs], reqs)
             sums = E.score_sums(prob, E.FAM_SQUARED, 0.0, eta, [table[i][4] for i in idxs],
                                 sets)
+        elif key[0] == "pn":
+            from . import pn
+            res, eta = pn.prox_newton(prob, reqs, stats=stats, comm=comm)
+            sums = E.score_sums(prob, E.FAM_TWEEDIE_LOG, key[1], eta,
+                                [table[i][4] for i in idxs], sets)
         else:
             res, sums = E.irls_scored(prob, reqs, sets, stats=stats, comm=comm,
                                       drop_sets=dsets)
