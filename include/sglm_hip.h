@@ -781,6 +781,14 @@ int sglm_lag_gram_pc(const int32_t* occ, const int32_t* ev_off, const uint32_t* 
  *   rsel[q] (q when NULL) of: f32 [*][ldr] (rmode 0); the packed three-piece bf16 buffer of
  *   sglm_link_update, [3][Bp][ldr] (rmode 2); one bf16 plane [*][ldr] (rmode 3).  pairs: device
  *   int32 [2][k] = {0 .. k-1, k .. k}.  Replaces the continuous coordinates of X^T (mu - y).
+ *   ldr % 4 == 0 and ldc % 4 == 0 (rows are read four at a time).  Padding rows: the sum runs
+ *   over r < n, but R is loaded in aligned groups of four rows, so the up to three rows
+ *   n .. 4 ceil(n / 4) - 1 of R are read and multiplied by 0.0: they must be FINITE (any value;
+ *   a NaN or Inf there would reach g).  Every producer keeps rows n .. ldr - 1 at zero: the link
+ *   kernels (sglm_link_update, sglm_link_update_rp, the fused trial-loss link) write 0 for every
+ *   row n <= r < ld of the f32 R and of the three packed pieces, sglm_digit_planes writes rows
+ *   < n of a zero-initialised plane, and the f32 digit rows of engine.xtv_digits are
+ *   zero-initialised.  Rows of R beyond 4 ceil(n / 4) and rows >= n of C are not read.
  * sglm_mixed_eta: eta[slot][r] += sum_c C[c][r] beta[slot][cpos[c]] (float64 sum, r < n) for
  *   slot = slots[q] (q when NULL), q < nb; k <= 1024.
  * sglm_mixed_to_h: H[slot][i][cpos[c]] = H[slot][cpos[c]][i] = f32(S[s][c][i]) for i < P,
