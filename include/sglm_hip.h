@@ -424,6 +424,10 @@ int sglm_chol_solve_alias(const float* H, int32_t P, const int32_t* fits, const 
  *   (state 1: its row of U zeroed, U_jj = 1, its column above the diagonal kept); state 0 =
  *   kept.  nulls[f][0 .. counts[2f]) = the dependent coordinates (ascending), counts[2f + 1] =
  *   dependent + zero columns.  work: sglm_chol64_work_bytes(P, nf).  P % 64 == 0, P <= 8192.
+ *   Only U[f][i][j] with i <= j is meaningful: the factor writes 0.0 below the diagonal inside
+ *   the 64 x 64 diagonal tiles and leaves the tiles below them untouched, and none of the calls
+ *   that take U (the solves, sglm_chol64_minnorm, the sglm_chol64_drop_* pair) reads an entry
+ *   with i > j -- a caller-built factor may hold anything there.
  * sglm_chol64_solve: delta[fits[q]] = -U_f^-1 U_f^-T g[fits[q]] (f32 out) on the kept
  *   coordinates of f = fsrc[q], 0 elsewhere (g float64 [*][P]).
  * sglm_chol64_minnorm: for each fit k = fits[q] on factor f = fsrc[q]: beta[k] (float64 [*][P])
@@ -440,7 +444,11 @@ int sglm_chol64_factor(const float* H, int32_t P, const int32_t* hsrc, const flo
  *   and columns of the continuous coordinates j (cmap[j] = c >= 0, cmap[j] = -1 elsewhere) are
  *   read from the float64 Gram block S[f][c][0 .. P) (sglm_mixed_gram, exact to rounding)
  *   instead of the f32 H, so that the rank decision of a continuous column is taken on its
- *   float64 Gram row (lstsq's float64 X, sklearn _base.py:701). */
+ *   float64 Gram row (lstsq's float64 X, sklearn _base.py:701).  Entry (i, j), i <= j, is
+ *   S[f][cmap[i]][j] when i is continuous, else S[f][cmap[j]][i] when j is: an entry between two
+ *   continuous coordinates comes from the S row of the one with the SMALLER index, the other
+ *   copy (S[f][cmap[j]][i]) is not read.  sglm_chol64_resid follows the same rule.  The rows and
+ *   columns of H at continuous coordinates are not read. */
 int sglm_chol64_factor_mixed(const float* H, int32_t P, const int32_t* hsrc, const float* dshift,
                              const double* lamp, const int32_t* dsrc, int32_t nf, double tol,
                              const double* S, int32_t k, const int32_t* cmap, double* U,
