@@ -42,8 +42,13 @@ enum sglm_status { SGLM_OK = 0, SGLM_EINVAL = 1, SGLM_EHIP = 2, SGLM_ENOTPD = 3 
  *  SGLM_FAM_SQUARED   : 0.5 (eta - y)^2, identity link (LinearRegression / Ridge /
  *                       TweedieRegressor(power=0) objectives; backend/sglm.py:96-105,116).
  *  SGLM_FAM_TWEEDIE_LOG: HalfTweedieLoss(power) with log link, power in [1, 2] covers
- *                       Poisson (1) and Gamma (2) (backend/sglm.py:112-115). */
-enum sglm_family { SGLM_FAM_SQUARED = 0, SGLM_FAM_TWEEDIE_LOG = 1 };
+ *                       Poisson (1) and Gamma (2) (backend/sglm.py:112-115).
+ *  SGLM_FAM_BINOMIAL_LOGIT: HalfBinomialLoss, softplus(eta) - y eta with the logit link, for
+ *                       responses y in {0, 1} (the GLM 'Binomial' name); `power` is not read.
+ *                       d loss/d eta = sigma(eta) - y, d2 loss/d eta2 = sigma (1 - sigma), both
+ *                       from e = exp(-|eta|): finite for every finite eta, the weight >= 0.
+ * Every entry that takes `family` accepts all three codes. */
+enum sglm_family { SGLM_FAM_SQUARED = 0, SGLM_FAM_TWEEDIE_LOG = 1, SGLM_FAM_BINOMIAL_LOGIT = 2 };
 
 enum sglm_xtype { SGLM_X_BF16 = 0, SGLM_X_F32 = 1 };
 
@@ -118,14 +123,17 @@ int sglm_gemv_eta(const void* X, int32_t xtype, int64_t ld, int32_t P, int64_t n
  * deta (optional, with step[q]): first eta[k] += step[q] * deta[k] (the previous Newton
  * step's predictor update, fused), then the link on the updated eta.
  * W may be NULL: the weights are then not stored (eta, R and Rp are what they are with W
- * given); sglm_link_weights writes them later from the eta this call leaves behind. */
+ * given); sglm_link_weights writes them later from the eta this call leaves behind.
+ * family SGLM_FAM_BINOMIAL_LOGIT: R = M (sigma(eta) - y), W = M sigma (1 - sigma) as
+ * e / (1 + e)^2 with e = exp(-|eta|) (no overflow, W >= 0; W underflows to 0 past |eta| ~ 87). */
 int sglm_link_update(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                      const int32_t* slots, float* eta, const float* Y, const uint8_t* M,
                      const int32_t* fit_resp, const int32_t* fit_mask, float* W, float* R,
                      void* Rp, const float* step, const float* deta, sglm_stream_t stream);
 /* sglm_link_update_rp: sglm_link_update (slots required) writing launch row y's packed R into
  * row rpos[y] of planes of Bp rows (rpos[y] < 0: no packed row; W, R and the fused predictor
- * update as usual) -- the rows of the fits that continue, compacted by sglm_step_decide. */
+ * update as usual) -- the rows of the fits that continue, compacted by sglm_step_decide.
+ * Every family of sglm_link_update. */
 int sglm_link_update_rp(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                         const int32_t* slots, float* eta, const float* Y, const uint8_t* M,
                         const int32_t* fit_resp, const int32_t* fit_mask, float* W, float* R,
@@ -135,7 +143,7 @@ int sglm_link_update_rp(int32_t family, float power, int64_t n, int64_t ld, int3
  * slots is NULL), q < B:  W[k][i] = M[m][i] * d2loss/deta2 at eta[k][i] for i < n, 0 for
  * n <= i < ld -- the same expression, so bitwise the W the link writes from that eta.  Rows of
  * W of other slots are not touched.  engine.irls links without W and calls this for the fits
- * whose Gram is about to be formed. */
+ * whose Gram is about to be formed.  Every family of sglm_link_update. */
 int sglm_link_weights(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                       const int32_t* slots, const float* eta, const float* Y, const uint8_t* M,
                       const int32_t* fit_resp, const int32_t* fit_mask, float* W,
@@ -572,6 +580,14 @@ int sglm_mask_stats(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, i
  * float64 terms and sums): out[q][j] - out[q][0], which is all a line search reads, is accurate
  * relative to its own size (about 1.3e-6 of sum M (mu |exp(t deta) - 1| + |y t deta|)), and
  * out[q][0] to f32 rounding of mu.  With deta = 0 the five outputs are bitwise equal.
+ * Binomial (SGLM_FAM_BINOMIAL_LOGIT) with the same t: differences too, from
+ *   l(t) - l(0) = log1p(sigma(eta) (exp(t deta) - 1)) - y t deta
+ * ((1 + e^(eta + s)) / (1 + e^eta) = 1 + sigma(eta) (e^s - 1)); exp(t deta) - 1 as for Poisson, one
+ * log1pf per trial, f32 factors, float64 terms and sums.  A row with |deta| > 3 takes the direct
+ * float64 losses and their differences instead: past it the f32 product loses the ratio to
+ * cancellation (sigma -> 1, exp(deta) - 1 -> -1) and later overflows (0 * inf).  No finite input
+ * gives NaN; with deta = 0 the five outputs are bitwise equal.
+ * Every other (family, power, T, t) sums float64 losses per trial.
  * The sums are two-level and deterministic: block partials per 8192-row chunk, then one wave per
  * output sums the chunks in a fixed order. */
 size_t sglm_rowsum_work_bytes(int32_t B, int32_t T, int64_t n);
@@ -582,7 +598,8 @@ int sglm_loss_trials(int32_t family, float power, int64_t n, int64_t ld, int32_t
 
 /* sglm_loss_trials plus dmax[q] = max over the rows of mask fit_mask[k] of |deta[k][i]| (B
  * floats, zeroed by the call): the step's predictor drift per unit step length, returned with
- * the trial losses so that the host needs one round trip per Newton iteration. */
+ * the trial losses so that the host needs one round trip per Newton iteration.  Every family
+ * and branch of sglm_loss_trials. */
 int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                          const int32_t* slots, const float* eta, const float* deta, const float* Y, const uint8_t* M,
                          const int32_t* fit_resp, const int32_t* fit_mask, const float* t,
@@ -602,6 +619,8 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
  * With out == NULL and dmax == NULL the call is the link alone (undo, eta and Rp as above, no
  * sums; t, T and work are not read): what engine.irls enqueues behind the read-back of
  * sglm_loss_trials_max's sums, so that the link runs while the host decides the steps.
+ * The contract holds for every family, SGLM_FAM_BINOMIAL_LOGIT and its difference branch
+ * included.
  * SGLM_EINVAL on a null pointer (one of out / dmax alone included), T != 5 with sums, Bp < B or
  * Bp % 32, n outside 1..ld, ld % 256. */
 int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
@@ -636,7 +655,8 @@ int sglm_eta_pair_absmax(int64_t n, int64_t ld, int32_t npairs, const int32_t* p
 /* Scores (GLM.score / get_residuals, backend/sglm.py:150-184, 314-331): for fit k and each
  * set s in {0, 1} with mask sets[2k + s] (-1 = empty):
  *   out[k][s][0] = sum_i M * (y_i - mu_i)^2,  out[k][s][1] = sum_i M * loss(y_i, eta_i),
- * mu = inverse link(eta).  `work`: sglm_rowsum_work_bytes(B, 4, n). */
+ * mu = inverse link(eta): eta, exp(eta), or sigma(eta) for SGLM_FAM_BINOMIAL_LOGIT (one
+ * exponential per row shared by mu and the loss).  `work`: sglm_rowsum_work_bytes(B, 4, n). */
 int sglm_score_sums(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                     const float* eta, const float* Y, const uint8_t* M,
                     const int32_t* fit_resp, const int32_t* sets, double* out, void* work,

@@ -328,6 +328,49 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
 }
 
 constexpr int kMaxTrials = 8;
+
+// Binomial (logit link) with the first-round step lengths {0, 1, 1/2, 1/4, 1/8}, one row: the
+// trials as differences, as the Poisson branch below sums them.  From
+//   (1 + e^(eta + s)) / (1 + e^eta) = 1 + sigma(eta) (e^s - 1):
+//   l(t) - l(0) = log1p(sigma(eta) x(t)) - y t d,   x(t) = exp(t d) - 1,
+// x from one expm1f(d/8) and three squarings, one log1pf per trial, f32 factors, the terms and
+// sums in float64, l(0) = max(eta, 0) + log1p(e^-|eta|) - y eta.  The f32 product holds the
+// ratio 1 + sigma x only while that is not small against sigma |x| <= 1: with sigma -> 1 and
+// x -> -1 it cancels (at d = -3 the ratio is still >= e^-3, an error of ~1e-7 / e^-3 on a term
+// of size 3), and at |d| ~ 88 x overflows against an underflowed sigma (0 * inf).  Rows with
+// |d| > kLogitDiffMaxD take the float64 losses and their differences instead -- exact to float64
+// rounding of l(0), NaN-free for every finite input.
+constexpr float kLogitDiffMaxD = 3.0f;
+// l(0) and l(t) - l(0) for t = 1, 1/2, 1/4, 1/8
+struct LogitTrials { double l0, d1, d2, d4, d8; };
+__device__ __forceinline__ LogitTrials logit_trials_row(float yi, float ei, float di) {
+    const double yd = (double)yi * (double)di;
+    LogitTrials o;
+    if (fabsf(di) <= kLogitDiffMaxD) {
+        const float e = expf(-fabsf(ei));
+        const float inv = 1.0f / (1.0f + e);
+        const float sg = ei >= 0.0f ? inv : e * inv;
+        const float x8 = expm1f(0.125f * di);
+        const float x4 = x8 * (2.0f + x8), x2 = x4 * (2.0f + x4), x1 = x2 * (2.0f + x2);
+        o.l0 = (double)fmaxf(ei, 0.0f) + (double)log1pf(e) - (double)yi * (double)ei;
+        o.d1 = (double)log1pf(sg * x1) - yd;
+        o.d2 = (double)log1pf(sg * x2) - 0.5 * yd;
+        o.d4 = (double)log1pf(sg * x4) - 0.25 * yd;
+        o.d8 = (double)log1pf(sg * x8) - 0.125 * yd;
+    } else {
+        const double z = ei, dd = di, yy = yi;
+        o.l0 = half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yy, z);
+        o.d1 = half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yy, z + dd) - o.l0;
+        o.d2 = half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yy, z + 0.5 * dd) - o.l0;
+        o.d4 = half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yy, z + 0.25 * dd) - o.l0;
+        o.d8 = half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yy, z + 0.125 * dd) - o.l0;
+    }
+    return o;
+}
+
+// LOGIT: the instantiation launched for SGLM_FAM_BINOMIAL_LOGIT (the other families run the
+// code they always ran).
+template <bool LOGIT>
 __global__ void __launch_bounds__(256) loss_trials_kernel(
     int32_t family, float power, int64_t n, int64_t ld, const float* __restrict__ eta,
     const float* __restrict__ deta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
@@ -336,6 +379,7 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
     float* __restrict__ dmax, const int32_t* __restrict__ slots) {
     __shared__ double sh[4];
     __shared__ float shm[4];
+    if constexpr (LOGIT) family = SGLM_FAM_BINOMIAL_LOGIT;
     const int q = blockIdx.y;                       // output row
     const int k = slots ? slots[q] : q;             // fit slot
     const int32_t nchunks = gridDim.x;
@@ -354,12 +398,19 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
     // with x(t) = exp(t d) - 1 from one expm1f(d/8) and three squarings x(2t) = x(t)(2 + x(t))
     // (no cancellation): two f32 transcendentals per row, the terms and sums in float64.
     // acc[0] holds L(0), acc[j >= 1] the difference; the block's partial of trial j is their sum.
-    const bool halving = family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f && T == 5 &&
+    // Binomial: the same layout from logit_trials_row.
+    const bool halving = (LOGIT || (family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f)) && T == 5 &&
                          tv[0] == 0.0f && tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f &&
                          tv[4] == 0.125f;
     if (halving) {
-        auto row = [&](double mi, float yi, float ei, float di) {
+        auto row = [&](double mi, float yi, float ei, float di) __attribute__((always_inline)) {
             mx = fmaxf(mx, fabsf(di));
+            if constexpr (LOGIT) {
+                const LogitTrials o = logit_trials_row(yi, ei, di);
+                acc[0] += mi * o.l0; acc[1] += mi * o.d1; acc[2] += mi * o.d2;
+                acc[3] += mi * o.d4; acc[4] += mi * o.d8;
+                return;
+            }
             const float muf = expf(ei), x8 = expm1f(0.125f * di);
             const float x4 = x8 * (2.0f + x8), x2 = x4 * (2.0f + x4), x1 = x2 * (2.0f + x2);
             const double mu = muf, yd = (double)yi * (double)di;
@@ -397,16 +448,33 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
             if (mi == 0.0) continue;
             const double yi = y[i], ei = e[i], di = d[i];
             mx = fmaxf(mx, fabsf((float)di));
-            for (int j = 0; j < T; ++j)
-                acc[j] += mi * half_loss_d(family, (double)power, yi, ei + (double)tv[j] * di);
+            if constexpr (LOGIT) {
+                // static indices: acc stays in registers next to the float64 log1p / exp
+#pragma unroll
+                for (int j = 0; j < kMaxTrials; ++j)
+                    if (j < T)
+                        acc[j] += mi * half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yi,
+                                                   ei + (double)tv[j] * di);
+            } else {
+                for (int j = 0; j < T; ++j)
+                    acc[j] += mi * half_loss_d<false>(family, (double)power, yi,
+                                                      ei + (double)tv[j] * di);
+            }
         }
     }
     double s0 = 0.0;
-    for (int j = 0; j < T; ++j) {
-        double s = block_sum_d(acc[j], sh);
+    auto put = [&](int j, double v) {
+        double s = block_sum_d(v, sh);
         if (j == 0) s0 = s;
         else if (halving) s += s0;
         if (threadIdx.x == 0) part[((int64_t)q * T + j) * nchunks + blockIdx.x] = s;
+    };
+    if constexpr (LOGIT) {
+#pragma unroll
+        for (int j = 0; j < kMaxTrials; ++j)
+            if (j < T) put(j, acc[j]);
+    } else {
+        for (int j = 0; j < T; ++j) put(j, acc[j]);
     }
     if (dmax) {                // max |d_eta| over the fit's rows (Hessian drift bound)
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
@@ -430,7 +498,7 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
 //    (the last chunk's block writes those).
 // A quad of four masked-out rows skips only the losses.
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-template <bool LOSS>
+template <bool LOSS, bool LOGIT>
 __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     int32_t family, float power, int64_t n, int64_t ld, float* __restrict__ eta,
     const float* __restrict__ deta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
@@ -440,6 +508,7 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     __bf16* __restrict__ Rp, int32_t Bp) {
     __shared__ double sh[4];
     __shared__ float shm[4];
+    if constexpr (LOGIT) family = SGLM_FAM_BINOMIAL_LOGIT;
     const int q = blockIdx.y;                       // output row = packed R row = undo row
     const int k = slots ? slots[q] : q;             // fit slot
     const int32_t nchunks = gridDim.x;
@@ -457,7 +526,7 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     const int64_t i1 = min(i0 + kRowChunk, n);
     // R of one row from the updated predictor, as link_kernel forms it
     auto link_row = [&](float mf, float yi, float en) {
-        const LossOut o = half_loss(family, power, yi, en);
+        const LossOut o = half_loss<LOGIT>(family, power, yi, en);
         return mf * o.g;
     };
     auto store_r = [&](int64_t i, float ri) {
@@ -470,11 +539,18 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     // LOSS = false: the link alone (no sums, tv / part / dmax not touched), four rows at a time
     bool halving = !LOSS;
     if constexpr (LOSS)
-        halving = family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f && T == 5 && tv[0] == 0.0f &&
-                  tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f && tv[4] == 0.125f;
+        halving = (LOGIT || (family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f)) && T == 5 &&
+                  tv[0] == 0.0f && tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f &&
+                  tv[4] == 0.125f;
     if (halving) {
-        auto row = [&](double mi, float yi, float ei, float di) {
+        auto row = [&](double mi, float yi, float ei, float di) __attribute__((always_inline)) {
             mx = fmaxf(mx, fabsf(di));
+            if constexpr (LOGIT) {
+                const LogitTrials o = logit_trials_row(yi, ei, di);
+                acc[0] += mi * o.l0; acc[1] += mi * o.d1; acc[2] += mi * o.d2;
+                acc[3] += mi * o.d4; acc[4] += mi * o.d8;
+                return;
+            }
             const float muf = expf(ei), x8 = expm1f(0.125f * di);
             const float x4 = x8 * (2.0f + x8), x2 = x4 * (2.0f + x4), x1 = x2 * (2.0f + x2);
             const double mu = muf, yd = (double)yi * (double)di;
@@ -560,8 +636,17 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
                 const float yr = y[i];
                 const double yi = yr, ei = eo, di = dr;
                 mx = fmaxf(mx, fabsf((float)di));
-                for (int j = 0; j < T; ++j)
-                    acc[j] += mi * half_loss_d(family, (double)power, yi, ei + (double)tv[j] * di);
+                if constexpr (LOGIT) {
+#pragma unroll
+                    for (int j = 0; j < kMaxTrials; ++j)
+                        if (j < T)
+                            acc[j] += mi * half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yi,
+                                                       ei + (double)tv[j] * di);
+                } else {
+                    for (int j = 0; j < T; ++j)
+                        acc[j] += mi * half_loss_d<false>(family, (double)power, yi,
+                                                          ei + (double)tv[j] * di);
+                }
                 ri = link_row((float)m[i], yr, en);
             }
             store_r(i, ri);
@@ -571,11 +656,18 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
         for (int64_t i = n + threadIdx.x; i < ld; i += 256) store_r(i, 0.0f);
     if constexpr (!LOSS) return;
     double s0 = 0.0;
-    for (int j = 0; j < T; ++j) {
-        double s = block_sum_d(acc[j], sh);
+    auto put = [&](int j, double v) {
+        double s = block_sum_d(v, sh);
         if (j == 0) s0 = s;
         else if (halving) s += s0;
         if (threadIdx.x == 0) part[((int64_t)q * T + j) * nchunks + blockIdx.x] = s;
+    };
+    if constexpr (LOGIT) {
+#pragma unroll
+        for (int j = 0; j < kMaxTrials; ++j)
+            if (j < T) put(j, acc[j]);
+    } else {
+        for (int j = 0; j < T; ++j) put(j, acc[j]);
     }
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = mx;
@@ -585,6 +677,7 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
                   __float_as_uint(fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]))));
 }
 
+template <bool LOGIT>
 __global__ void __launch_bounds__(256) score_kernel(
     int32_t family, float power, int64_t n, int64_t ld, const float* __restrict__ eta,
     const float* __restrict__ Y, const uint8_t* __restrict__ M,
@@ -608,9 +701,17 @@ __global__ void __launch_bounds__(256) score_kernel(
         const double yi = y[i], ei = e[i];
         // Poisson: mu = exp(eta) is also the loss's exponential, evaluated once
         const bool pois = family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f;
-        const double mu = inv_link_d(family, ei);
+        double mu, l;
+        if constexpr (LOGIT) {
+            // logit: exp(-|eta|) gives both sigma(eta) and softplus(eta)
+            const double ex = exp(-fabs(ei));
+            mu = ei >= 0.0 ? 1.0 / (1.0 + ex) : ex / (1.0 + ex);
+            l = fmax(ei, 0.0) + log1p(ex) - yi * ei;
+        } else {
+            mu = inv_link_d<false>(family, ei);
+            l = pois ? mu - yi * ei : half_loss_d<false>(family, (double)power, yi, ei);
+        }
         const double r2 = (yi - mu) * (yi - mu);
-        const double l = pois ? mu - yi * ei : half_loss_d(family, (double)power, yi, ei);
         acc[0] += w0 * r2; acc[1] += w0 * l;
         acc[2] += w1 * r2; acc[3] += w1 * l;
     }
@@ -1294,7 +1395,10 @@ int sglm_loss_trials(int32_t family, float power, int64_t n, int64_t ld, int32_t
     (void)ld;
     const int32_t nc = row_chunks(n);
     hipStream_t s = as_stream(stream);
-    loss_trials_kernel<<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
+    if (family == SGLM_FAM_BINOMIAL_LOGIT)
+        loss_trials_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
+    else
+        loss_trials_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
     int st = check_launch("loss_trials_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
@@ -1317,7 +1421,10 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
         set_error("sglm_loss_trials_max: hipMemsetAsync failed");
         return SGLM_EHIP;
     }
-    loss_trials_kernel<<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
+    if (family == SGLM_FAM_BINOMIAL_LOGIT)
+        loss_trials_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
+    else
+        loss_trials_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
     int st = check_launch("loss_trials_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
@@ -1340,19 +1447,31 @@ int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, in
     }
     const int32_t nc = row_chunks(n);
     hipStream_t s = as_stream(stream);
+    const bool logit = family == SGLM_FAM_BINOMIAL_LOGIT;
+    const dim3 grid((unsigned)nc, (unsigned)B);
     if (link_only) {
-        loss_trials_link_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(
-            family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
-            nullptr, slots, undo, (__bf16*)Rp, Bp);
+        if (logit)
+            loss_trials_link_kernel<false, true><<<grid, 256, 0, s>>>(
+                family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
+                nullptr, slots, undo, (__bf16*)Rp, Bp);
+        else
+            loss_trials_link_kernel<false, false><<<grid, 256, 0, s>>>(
+                family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
+                nullptr, slots, undo, (__bf16*)Rp, Bp);
         return check_launch("loss_trials_link_kernel<link only>");
     }
     if (hipMemsetAsync(dmax, 0, sizeof(float) * (size_t)B, s) != hipSuccess) {
         set_error("sglm_loss_trials_link: hipMemsetAsync failed");
         return SGLM_EHIP;
     }
-    loss_trials_link_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(
-        family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
-        slots, undo, (__bf16*)Rp, Bp);
+    if (logit)
+        loss_trials_link_kernel<true, true><<<grid, 256, 0, s>>>(
+            family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
+            slots, undo, (__bf16*)Rp, Bp);
+    else
+        loss_trials_link_kernel<true, false><<<grid, 256, 0, s>>>(
+            family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
+            slots, undo, (__bf16*)Rp, Bp);
     int st = check_launch("loss_trials_link_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
@@ -1494,7 +1613,10 @@ int sglm_score_sums(int32_t family, float power, int64_t n, int64_t ld, int32_t 
     if (!eta || !Y || !M || !fit_resp || !sets || !out || !work) { set_error("sglm_score_sums: null pointer"); return SGLM_EINVAL; }
     const int32_t nc = row_chunks(n);
     hipStream_t s = as_stream(stream);
-    score_kernel<<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
+    if (family == SGLM_FAM_BINOMIAL_LOGIT)
+        score_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
+    else
+        score_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
     int st = check_launch("score_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * 4;

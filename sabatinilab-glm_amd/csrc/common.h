@@ -26,14 +26,26 @@ __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) {
 }
 
 // Per-sample half-Tweedie loss pieces (sklearn/_loss/loss.py), single precision.
-// family 0: 0.5 (eta - y)^2 (identity); family 1: HalfTweedieLoss(power), log link.
+// family 0: 0.5 (eta - y)^2 (identity); family 1: HalfTweedieLoss(power), log link;
+// family 2: HalfBinomialLoss softplus(eta) - y eta, logit link (power not read), everything
+// from e = exp(-|eta|) in (0, 1]: no overflow at any finite eta, h = sigma (1 - sigma) >= 0.
+// LOGIT = false leaves the family-2 code out: kernels instantiated for the families 0 / 1 alone
+// (the trial-loss and score passes) keep the registers and occupancy they had without it.
 struct LossOut { float loss, g, h; };
 
+template <bool LOGIT = true>
 __device__ __forceinline__ LossOut half_loss(int family, float power, float y, float eta) {
     LossOut o;
     if (family == SGLM_FAM_SQUARED) {
         float r = eta - y;
         o.loss = 0.5f * r * r; o.g = r; o.h = 1.0f;
+    } else if (LOGIT && family == SGLM_FAM_BINOMIAL_LOGIT) {
+        const float e = __expf(-fabsf(eta));
+        const float inv = 1.0f / (1.0f + e);
+        const float sigma = eta >= 0.0f ? inv : e * inv;
+        o.loss = fmaxf(eta, 0.0f) + log1pf(e) - y * eta;
+        o.g = sigma - y;
+        o.h = e * inv * inv;
     } else if (power == 1.0f) {
         float mu = __expf(eta);
         o.loss = mu - y * eta; o.g = mu - y; o.h = mu;
@@ -51,14 +63,22 @@ __device__ __forceinline__ LossOut half_loss(int family, float power, float y, f
 }
 
 // double-precision loss for reductions that decide line searches / scores
+template <bool LOGIT = true>
 __device__ __forceinline__ double half_loss_d(int family, double power, double y, double eta) {
     if (family == SGLM_FAM_SQUARED) { double r = eta - y; return 0.5 * r * r; }
+    if (LOGIT && family == SGLM_FAM_BINOMIAL_LOGIT)
+        return fmax(eta, 0.0) + log1p(exp(-fabs(eta))) - y * eta;
     if (power == 1.0) return exp(eta) - y * eta;
     if (power == 2.0) return eta + y * exp(-eta);
     return exp((2.0 - power) * eta) / (2.0 - power) - y * exp((1.0 - power) * eta) / (1.0 - power);
 }
 
+template <bool LOGIT = true>
 __device__ __forceinline__ double inv_link_d(int family, double eta) {
+    if (LOGIT && family == SGLM_FAM_BINOMIAL_LOGIT) {        // the logistic function, no overflow
+        const double e = exp(-fabs(eta));
+        return eta >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+    }
     return family == SGLM_FAM_SQUARED ? eta : exp(eta);
 }
 

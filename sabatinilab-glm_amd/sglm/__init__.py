@@ -11,7 +11,10 @@ Behaviour fixed on purpose (SURVEY.md §7 "Reference defects"), API unchanged:
     and raises AttributeError, :246-251);
   * ``alpha == 0`` without ``l1_ratio``/``max_iter`` no longer raises KeyError (:97-99);
   * ``NotYetImplementedError`` is defined (the reference raises an undefined name).
-Logistic/Multinomial and the PCA warm-start are out of scope.
+``'Binomial'`` (which the reference lists but never implemented) is the Bernoulli GLM with the
+logit link in the Tweedie families' mean-scaled objective (``BinomialRegressor``); responses are
+exactly 0 or 1, ``predict`` returns the probability.  Logistic/Multinomial (sklearn's
+``LogisticRegression`` surface) and the PCA warm-start are out of scope.
 """
 from __future__ import annotations
 
@@ -22,9 +25,9 @@ import numpy as np
 import pandas as pd
 import scipy.stats
 
-from sglm_hip.estimators import (ElasticNet, Lasso, LinearRegression, LogisticRegression,  # noqa: F401
-                                 NotYetImplementedError, PoissonRegressor, Ridge,
-                                 TweedieRegressor, host_matrix)
+from sglm_hip.estimators import (BinomialRegressor, ElasticNet, Lasso, LinearRegression,  # noqa: F401
+                                 LogisticRegression, NotYetImplementedError, PoissonRegressor,
+                                 Ridge, TweedieRegressor, host_matrix)
 
 
 class GLM():
@@ -61,6 +64,8 @@ class GLM():
             Base = TweedieRegressor
         elif model_name in {'Tweedie'}:
             Base = TweedieRegressor
+        elif model_name in {'Binomial'}:
+            Base = BinomialRegressor
         elif model_name in {'Logistic', 'Multinomial'}:
             kwargs['multi_class'] = 'multinomial' if model_name == 'Multinomial' else 'auto'
             kwargs['n_jobs'] = kwargs['n_jobs'] if 'n_jobs' in kwargs else -1

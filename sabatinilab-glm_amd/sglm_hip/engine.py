@@ -43,6 +43,7 @@ except ImportError as e:  # pragma: no cover - torch is part of the image
 
 FAM_SQUARED = 0
 FAM_TWEEDIE_LOG = 1
+FAM_BINOMIAL_LOGIT = 2         # HalfBinomialLoss, logit link, y in {0, 1} (power not read)
 X_BF16, X_F32 = 0, 1
 COL_PAD = 256
 ROW_PAD = 256
@@ -1751,6 +1752,12 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     warm = any(r.coef0 is not None for r in reqs)
     beta = np.zeros((B0, P), dtype=np.float64) if warm else None
     for k, r in enumerate(reqs):
+        if fam == FAM_BINOMIAL_LOGIT:
+            # one class on the fit's rows: no finite optimum (and no logit(mean y) to start at)
+            # (sum y counts the ones; rounded: the grid's centred device sums carry rounding)
+            cnt, s, ym = prob.mask_stats(r.resp, r.mask)
+            if cnt and not 0 < round(s) < round(cnt):
+                raise ValueError("Binomial fit on rows whose responses are all 0 or all 1")
         if r.coef0 is not None:
             beta[k, :p] = r.coef0
             icpt[k] = (r.intercept0 or 0.0) if r.fit_intercept else 0.0
@@ -1760,6 +1767,8 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
                 if ym <= 0:
                     raise ValueError("Some value(s) of y are out of the valid range of the loss")
                 icpt[k] = math.log(ym)
+            elif fam == FAM_BINOMIAL_LOGIT:
+                icpt[k] = math.log(ym / (1.0 - ym)) if cnt else 0.0
             else:
                 icpt[k] = ym
     fi = np.array([1.0 if r.fit_intercept else 0.0 for r in reqs])
@@ -1793,9 +1802,11 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         d.eta(bf.beta, bf.eta)
 
     const_hess = fam == FAM_SQUARED
-    reuse_tol = 0.0 if const_hess else HESS_REUSE_TOL / max(1.0, abs(2.0 - power))
-    share_tol = 0.0 if const_hess else min(HESS_SHARE_TOL / max(1.0, abs(2.0 - power)),
-                                           reuse_tol)
+    # drift divisor c of the weight bound e^(c D): |2 - power| for the log link; the logit
+    # weight has d ln h / d eta = 1 - 2 mu in (-1, 1), so c = 1 as for Poisson
+    drift_c = 1.0 if fam == FAM_BINOMIAL_LOGIT else max(1.0, abs(2.0 - power))
+    reuse_tol = 0.0 if const_hess else HESS_REUSE_TOL / drift_c
+    share_tol = 0.0 if const_hess else min(HESS_SHARE_TOL / drift_c, reuse_tol)
     # Device state is held per SLOT (one per fit, fixed for the whole solve); every per-fit
     # kernel takes the list of active slots, so stopped fits cost nothing and no state moves.
     B = B0
@@ -1859,8 +1870,10 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
         mall = dict(zip(umask, (flag.cpu().numpy() > 0).tolist()))
     all_rows = np.array([mall[int(r.mask)] for r in reqs])
     # the weight m * h(y, eta) is one constant on such a mask only when h does not depend on y:
-    # the Poisson log link (h = exp(eta)); Gamma / Tweedie's h carries y on every row
-    use_lag_gram = (LAG_GRAM and fam == FAM_TWEEDIE_LOG and power == 1.0 and d.lag is not None
+    # the Poisson log link (h = exp(eta)) and the logit link (h = mu (1 - mu)); Gamma /
+    # Tweedie's h carries y on every row
+    use_lag_gram = (LAG_GRAM and ((fam == FAM_TWEEDIE_LOG and power == 1.0)
+                                  or fam == FAM_BINOMIAL_LOGIT) and d.lag is not None
                     and getattr(d.lag, "ebits", None) is not None
                     and d.lag.smax - d.lag.smin <= 2048)
     fowner = np.zeros(B0, dtype=np.int64)
@@ -1894,7 +1907,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     bf.wlink = (fam, power, n, ld, prob.Y, prob.M, fit_resp, fit_mask)
     bf.mixS = {}
     # cross-mask families (slot of the representative per slot, -1: none / is one)
-    xmask_tol = 0.0 if const_hess else HESS_XMASK_TOL / max(1.0, abs(2.0 - power))
+    xmask_tol = 0.0 if const_hess else HESS_XMASK_TOL / drift_c
     repl = np.full(B0, -1, dtype=np.int64)
     if xmask_tol > 0.0:
         fams = {}
@@ -3365,7 +3378,8 @@ def _partition(reqs: List[FitReq], ngroups: int, rows=None) -> List[List[int]]:
     the lighter group (fits of one mask share their first Hessian and the lambda-path Hessian
     sharing); with fewer masks than groups the largest mask's fits are dealt alternately in
     penalty order."""
-    if (rows is not None and HESS_XMASK_TOL > 0 and reqs[0].family == FAM_TWEEDIE_LOG):
+    if (rows is not None and HESS_XMASK_TOL > 0
+            and reqs[0].family in (FAM_TWEEDIE_LOG, FAM_BINOMIAL_LOGIT)):
         fams = {}
         for i, r in enumerate(reqs):
             fams.setdefault(_family_key(r, rows[i]) or ("solo", i), []).append(i)

@@ -14,6 +14,9 @@ kwargs), and replace their numerics with the batched IRLS engine:
   Lasso/ElasticNet  1/(2n)||.||^2 + a rho |w|_1 + a(1-rho)/2 ||w||^2 -> Gram-space CD
   TweedieRegressor(l1_ratio=rho > 0), log link:
                     mean loss + a rho |w|_1 + a(1-rho)/2 ||w||^2 -> proximal Newton (pn.py)
+  BinomialRegressor mean [softplus(eta) - y eta] + alpha/2 ||w||^2, y in {0, 1}, logit link
+                    (sklearn's HalfBinomialLoss in the TweedieRegressor objective; the GLM
+                    'Binomial' name) -> lam = alpha * n_train
 """
 from __future__ import annotations
 
@@ -63,6 +66,17 @@ def _check_y_range(power: float, y: np.ndarray):
     if bad:
         name = {1: "HalfPoissonLoss", 2: "HalfGammaLoss"}.get(power, "HalfTweedieLoss")
         raise ValueError(f"Some value(s) of y are out of the valid range of the loss {name!r}.")
+
+
+def check_binomial_y(y) -> np.ndarray:
+    """The response of a Binomial fit as float64: bool / int / float values that are exactly 0
+    or 1 on every row (host check, before any device work)."""
+    y = np.asarray(y)
+    if y.dtype == object:
+        y = y.astype(np.float64)
+    if not np.all((y == 0) | (y == 1)):
+        raise ValueError("Binomial responses must be 0 or 1")
+    return y.astype(np.float64).reshape(-1)
 
 
 def host_matrix(X):
@@ -210,11 +224,13 @@ class _EngineRegressor:
             raise NotYetImplementedError("sample_weight is not used by the reference path")
         Xh = X
         X = _as2d(X)
+        obj = self.objective()
+        if obj.family == E.FAM_BINOMIAL_LOGIT:
+            y = check_binomial_y(y)
         y = np.asarray(y, dtype=np.float64).reshape(-1)
         if X.shape[0] != y.shape[0]:
             raise ValueError(f"Found input variables with inconsistent numbers of samples: "
                              f"[{X.shape[0]}, {y.shape[0]}]")
-        obj = self.objective()
         _check_y_range(obj.power if obj.family == E.FAM_TWEEDIE_LOG else 0, y)
         d = self._design(Xh)
         prob = E.Problem(d, [y], [np.ones(X.shape[0], np.uint8)])
@@ -260,6 +276,8 @@ class _EngineRegressor:
     def predict(self, X):
         eta = self._linear_predictor(X)
         obj = self.objective()
+        if obj.family == E.FAM_BINOMIAL_LOGIT:
+            return sigmoid_np(eta)
         return np.exp(eta) if obj.family == E.FAM_TWEEDIE_LOG else eta
 
     def score(self, X, y, sample_weight=None):
@@ -410,6 +428,45 @@ class PoissonRegressor(TweedieRegressor):
                          verbose=verbose, l1_ratio=l1_ratio)
 
 
+class BinomialRegressor(_EngineRegressor):
+    """Bernoulli GLM with the logit link in TweedieRegressor's mean-scaled objective,
+    mean_i [softplus(eta_i) - y_i eta_i] + alpha/2 |w|^2 (unpenalised intercept): the minimiser
+    of sklearn LogisticRegression(C = 1 / (alpha n)).  Responses are exactly 0 or 1."""
+    _params = ("alpha", "fit_intercept", "solver", "max_iter", "tol", "warm_start", "verbose",
+               "l1_ratio")
+
+    def __init__(self, *, alpha=1.0, fit_intercept=True, solver="lbfgs", max_iter=100, tol=1e-4,
+                 warm_start=False, verbose=0, l1_ratio=0.0):
+        super().__init__(alpha=alpha, fit_intercept=fit_intercept, solver=solver,
+                         max_iter=max_iter, tol=tol, warm_start=warm_start, verbose=verbose,
+                         l1_ratio=l1_ratio)
+
+    def objective(self):
+        if self.alpha < 0:
+            raise ValueError("alpha must be >= 0")
+        rho = float(self.l1_ratio)
+        if not 0.0 <= rho <= 1.0:
+            raise ValueError(f"The 'l1_ratio' parameter of {type(self).__name__} must be a float "
+                             f"in the range [0.0, 1.0]. Got {self.l1_ratio!r} instead.")
+        if rho > 0.0 and self.alpha > 0:
+            raise NotYetImplementedError("BinomialRegressor(l1_ratio > 0): elastic-net penalties "
+                                         "on the logit link")
+        return Objective("irls", E.FAM_BINOMIAL_LOGIT, 0.0, float(self.alpha), "n",
+                         self.fit_intercept, int(self.max_iter))
+
+    def decision_function(self, X):
+        """The linear predictor eta = X w + b."""
+        return self._linear_predictor(X)
+
+    def score(self, X, y, sample_weight=None):
+        """D^2, the fraction of binomial deviance explained (as TweedieRegressor.score; the
+        loss constant of 0/1 labels is 0)."""
+        y = check_binomial_y(y)
+        dev = np.sum(binomial_loss_np(y, self._linear_predictor(X)))
+        dev0 = binomial_null_np(float(y.size), float(y.mean()))
+        return 1.0 - dev / dev0 if dev0 > 0 else (1.0 if dev == 0 else 0.0)
+
+
 class LogisticRegression:
     """Out of scope: the reference's Logistic/Multinomial path."""
 
@@ -425,6 +482,25 @@ def half_loss_np(power, y, eta):
     if power == 2:
         return eta + y * np.exp(-eta)
     return np.exp((2 - power) * eta) / (2 - power) - y * np.exp((1 - power) * eta) / (1 - power)
+
+
+def sigmoid_np(eta):
+    """Host float64 logistic function, no overflow."""
+    e = np.exp(-np.abs(eta))
+    return np.where(eta >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def binomial_loss_np(y, eta):
+    """Host float64 half-binomial loss softplus(eta) - y eta (logit link) for scores only."""
+    return np.maximum(eta, 0.0) + np.log1p(np.exp(-np.abs(eta))) - y * eta
+
+
+def binomial_null_np(cnt: float, ym: float) -> float:
+    """Summed loss of 0/1 labels with mean ``ym`` over ``cnt`` rows at eta = logit(ym), in closed
+    form: -cnt (ym ln ym + (1 - ym) ln(1 - ym)); 0 when every label is the same."""
+    if not 0.0 < ym < 1.0:
+        return 0.0
+    return -cnt * (ym * math.log(ym) + (1.0 - ym) * math.log1p(-ym))
 
 
 def loss_constant_np(power, y):

@@ -34,8 +34,9 @@ from .estimators import Objective
 class _MaskStats:
     """float64 statistics of every (response, mask) pair that the scores and the y-range check
     need: count, mean, sum of squares about the mean, min y; per Tweedie power the summed
-    loss constant and null deviance.  One pass of sglm_mask_stats over the device masks and
-    responses per power (the reference computes them per fold on host copies,
+    loss constant and null deviance (``power="binomial"``: constant 0 for 0/1 labels, the null
+    deviance in closed form from the counts, no device pass).  One pass of sglm_mask_stats over
+    the device masks and responses per power (the reference computes them per fold on host copies,
     backend/sglm.py:150-184, 388-408)."""
 
     def __init__(self, prob: E.Problem, comm=None):
@@ -96,7 +97,13 @@ class _MaskStats:
         cnt = float(self.cnt[m])
         ym = float(self.mean[m, r])
         out = {"cnt": cnt, "mean": ym, "sst": float(self.sst[m, r]), "ymin": float(self.ymin[m, r])}
-        if power is not None and cnt:
+        if power == "binomial":
+            if cnt:
+                from .estimators import binomial_null_np
+                out["const"] = 0.0
+                # the number of ones is an integer: exact from the rounded sum
+                out["null"] = binomial_null_np(cnt, round(float(self.sy[m, r])) / cnt)
+        elif power is not None and cnt:
             out["const"] = float(self._consts(power)[m, r])
             sy = float(self.sy[m, r])
             if ym > 0:                   # sum of half_loss(y, log(mean)) in closed form
@@ -292,7 +299,7 @@ def rank_share(plan, groups: Sequence[dict], rank: int, world: int):
         units.setdefault((t[0], t[1]), []).append(i)
     fam = (world > 1 and SHARD_PLAN == "mask_major" and E.HESS_XMASK_TOL > 0
            and len(units) >= world
-           and all(o.kind == "irls" and o.family == E.FAM_TWEEDIE_LOG
+           and all(o.kind == "irls" and o.family in (E.FAM_TWEEDIE_LOG, E.FAM_BINOMIAL_LOGIT)
                    for g in groups for o in g["objectives"]))
     if fam:
         # whole parameters (a penalty's split fits + refit: one cross-mask family, solved on
@@ -332,6 +339,9 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
     from .comm import RowComm, SimComm, row_slab
     dist = _dist() if shard and simulate is None else None
     irls_only = all(o.kind == "irls" for g in groups for o in g["objectives"])
+    if any(o.family == E.FAM_BINOMIAL_LOGIT for g in groups for o in g["objectives"]):
+        from .estimators import check_binomial_y
+        y = check_binomial_y(y)              # every row, before any device work
     comm = None
     if isinstance(simulate, SimComm):
         comm = simulate                          # one rank of a row-sharded solve, simulated
@@ -398,18 +408,26 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
     # sklearn's y-range check of the log-link fits (y >= 0 on the fit's rows, positive mean;
     # glm.py:231-235), on this rank's fits from the device mask statistics; the verdict is
     # shared (one int all-reduce) so that every rank raises together
+    # (a Binomial fit needs both classes on its rows: 0 < mean < 1; verdict 2)
     bad = 0
     for i in mine:
         _, _, _, m, r, _ = table[i]
-        if groups[table[i][0]]["objectives"][table[i][1]].family == E.FAM_TWEEDIE_LOG:
+        fam_i = groups[table[i][0]]["objectives"][table[i][1]].family
+        if fam_i == E.FAM_TWEEDIE_LOG:
             st_ = ms.get(r, local[m])
-            bad |= int(bool(st_["cnt"]) and (st_["ymin"] < 0 or st_["mean"] <= 0))
+            bad = max(bad, int(bool(st_["cnt"]) and (st_["ymin"] < 0 or st_["mean"] <= 0)))
+        elif fam_i == E.FAM_BINOMIAL_LOGIT:
+            st_ = ms.get(r, local[m])
+            ones = round(st_["mean"] * st_["cnt"])       # the centred sums carry rounding
+            bad = max(bad, 2 * int(bool(st_["cnt"]) and not 0 < ones < round(st_["cnt"])))
     if dist is not None and comm is None:
         import torch
         flag = torch.tensor([bad], dtype=torch.int32,
                             device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(flag, op=dist.ReduceOp.MAX)
         bad = int(flag.item())
+    if bad == 2:
+        raise ValueError("Binomial fit on rows whose responses are all 0 or all 1")
     if bad:
         raise ValueError("Some value(s) of y are out of the valid range of the loss "
                          "'HalfPoissonLoss'.")
@@ -463,7 +481,8 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
             rr = res[q]
             _, _, k, m, r, mt = table[i]
             obj = objective(i)
-            pw = obj.power if obj.family == E.FAM_TWEEDIE_LOG else None
+            pw = (obj.power if obj.family == E.FAM_TWEEDIE_LOG
+                  else "binomial" if obj.family == E.FAM_BINOMIAL_LOGIT else None)
             sc = {}
             if k < 0:
                 if mt >= 0:
@@ -590,4 +609,6 @@ def _score(method, obj: Objective, sums, st):
         if st["sst"] == 0:
             return 1.0 if s2 == 0 else 0.0
         return 1.0 - s2 / st["sst"]
+    if obj.family == E.FAM_BINOMIAL_LOGIT and st["null"] == 0:    # one class on the scored rows
+        return 1.0 if sl == 0 else 0.0
     return 1.0 - (sl + st["const"]) / (st["null"] + st["const"])

@@ -6,7 +6,8 @@ lags ``[-L, ..., L-1]`` expanded in the shift-major layout of
 the first ``L-1`` and last ``L`` rows of the expansion hold the NaN fill and are dropped, so
 ``N_raw = N + 2L - 1`` leaves exactly ``N`` rows.  ``beta_true ~ N(0, 0.1^2)`` (rng 1);
 Poisson ``y ~ Poisson(exp(X beta + b))`` with ``b = -1`` (rng 2); Gaussian
-``y = X beta + 0.5 + N(0, 1)``.  Trial ids ``t // 100``.
+``y = X beta + 0.5 + N(0, 1)``; Binomial ``y ~ Bernoulli(sigma(X beta + b))`` (rng 2, one uniform
+draw per row).  Trial ids ``t // 100``.
 
 The linear predictor is computed by per-event convolution of E with the lag kernel, so the
 1M x 2000 design never has to exist on the host.
@@ -68,6 +69,8 @@ def make(N, m, L, family="poisson", rho=0.02, seed=0, beta_scale=0.1, intercept=
     elif family == "gamma":
         mu = np.exp(eta)
         y = rng2.gamma(2.0, mu / 2.0)
+    elif family == "binomial":
+        y = (rng2.random(N) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
     else:
         y = eta + rng2.normal(0.0, 1.0, size=N)
     trial = np.arange(N) // 100
