@@ -1009,6 +1009,31 @@ int sglm_pn_update(int32_t P, int32_t p, const int32_t* slots, int32_t nfit, con
                    const double* u, const double* rec, int32_t rec_stride, double* beta,
                    sglm_stream_t stream);
 
+/* Group lasso on shared Grams (one penalty term per column group, e.g. per event kernel):
+ *   1/2 w^T Q w - q^T w + sum_g lam_g |w_g|_2 + l2/2 |w|^2,  lam_g = lam_scale sqrt(k_g),
+ * the ElasticNet objective of sglm_enet_cd_shared when every group is one column.  The groups
+ * are a CSR in DEVICE memory: goff [ng + 1] (0 = goff[0] < ... < goff[ng] = p) and gcols [p], a
+ * permutation of 0..p-1 (group g = columns gcols[goff[g] .. goff[g+1]), k_g of them, need not be
+ * contiguous).  Both entry points read the CSR back and check it (one stream synchronisation);
+ * p <= 4096.  Float64 throughout.
+ * sglm_group_bound: gamma[m][g] (nq x ng) >= lambda_max of the block of Q[m] (nq matrices, p x p)
+ *   on group g: its largest absolute row sum (exact for k_g = 1, times 1 + 1e-12 otherwise).
+ * sglm_group_cd_shared: per fit f, block-wise majorised descent (Yang & Zou) on Q[qidx[f]],
+ *   q[f] from w = 0: z = w_g + (q_g - (Q w)_g - l2 w_g) / G, G = gamma[qidx[f]][g] + l2[f];
+ *   w_g <- z max(0, 1 - lam_g / (G |z|)), exact 0.0 when |z| <= lam_g / G; sweeps over the groups
+ *   in order until max|dw| <= tol max|w| over a sweep or max_sweeps sweeps -> w[f] (p),
+ *   sweeps[f].  A workgroup solves sglm_group_cd_fits_per_wg(p) consecutive fits; those of equal
+ *   qidx share every row of Q read, so callers sort the fits by qidx.  The norm |z| is summed
+ *   in a fixed order: a repeated call returns the same bits. */
+int32_t sglm_group_cd_fits_per_wg(int32_t p);
+int sglm_group_bound(const double* Q, int32_t p, int32_t nq, const int32_t* goff,
+                     const int32_t* gcols, int32_t ng, double* gamma, sglm_stream_t stream);
+int sglm_group_cd_shared(const double* Q, int32_t p, const int32_t* qidx, int32_t nfit,
+                         const double* q, const int32_t* goff, const int32_t* gcols, int32_t ng,
+                         const double* gamma, const double* lam_scale, const double* l2,
+                         int32_t max_sweeps, double tol, double* w, int32_t* sweeps,
+                         sglm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,9 +25,9 @@ import numpy as np
 import pandas as pd
 import scipy.stats
 
-from sglm_hip.estimators import (BinomialRegressor, ElasticNet, Lasso, LinearRegression,  # noqa: F401
-                                 LogisticRegression, NotYetImplementedError, PoissonRegressor,
-                                 Ridge, TweedieRegressor, host_matrix)
+from sglm_hip.estimators import (BinomialRegressor, ElasticNet, GroupLasso, Lasso,  # noqa: F401
+                                 LinearRegression, LogisticRegression, NotYetImplementedError,
+                                 PoissonRegressor, Ridge, TweedieRegressor, host_matrix)
 
 
 class GLM():
@@ -43,17 +43,27 @@ class GLM():
             kwargs['warm_start'] = True
 
         self.model_name = model_name
+        # groups (one id per column): the group lasso, Normal / Gaussian only
+        if kwargs.get('groups', 0) is None:
+            del kwargs['groups']
+        if 'groups' in kwargs and model_name not in {'Normal', 'Gaussian'}:
+            raise NotYetImplementedError(f"groups (group-lasso penalty) on {model_name!r}: "
+                                         "Normal / Gaussian only")
         if model_name in {'Normal', 'Gaussian'}:
             if 'alpha' in kwargs and kwargs['alpha'] == 0:
                 kwargs.pop('alpha')
                 kwargs.pop('l1_ratio', None)
+                kwargs.pop('groups', None)
                 kwargs.pop('max_iter', None)
                 kwargs.pop('warm_start', None)
                 Base = LinearRegression
             elif 'l1_ratio' in kwargs and kwargs['l1_ratio'] == 0:
                 del kwargs['l1_ratio']
                 kwargs.pop('warm_start', None)
+                kwargs.pop('groups', None)
                 Base = Ridge
+            elif 'groups' in kwargs:
+                Base = GroupLasso
             elif 'l1_ratio' in kwargs and kwargs['l1_ratio'] == 1:
                 del kwargs['l1_ratio']
                 Base = Lasso

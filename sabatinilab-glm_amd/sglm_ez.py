@@ -173,6 +173,29 @@ def left_out_columns(X, left_out):
     return sorted(out)
 
 
+def event_groups(X):
+    """Group-id array (length = number of columns, ids 0, 1, ... in order of first appearance)
+    of a lagged frame for ``GLM(..., groups=...)``: one id per base column name, covering the
+    name's own column and all its shifted columns -- ``left_out_columns``'s rule: by the lagged
+    frame's own column-to-source map while it is lazy, else by ``add_timeshifts_to_col_list``'s
+    naming (``f"{name}_{shift}"`` belongs to ``name`` when the frame has a column ``name``).  A
+    column that is no shift of another column is a group of its own."""
+    import re
+    cols = list(X.columns)
+    spec = X._spec if isinstance(X, LagFrame) and X.is_lazy else None
+    names = set(str(c) for c in cols)
+    pat = re.compile(r"(.+)_(-?\d+)$")
+    ids, out = {}, []
+    for c in cols:
+        if spec is not None:
+            base = c if c in X._overlay else spec[c][0]
+        else:
+            m = pat.match(str(c))
+            base = m.group(1) if m and m.group(1) in names else str(c)
+        out.append(ids.setdefault(base, len(ids)))
+    return np.asarray(out, dtype=np.int64)
+
+
 def reduce_cv_result(r, drop, glm_kwargs, model_name):
     """One parameter's grid result dict (full length p, zeros on the dropped columns ``drop``)
     as the reference's loop over column-deleted frames reports it: coefficients of the kept

@@ -193,6 +193,10 @@ SIGNATURES = {
     "sglm_pn_step": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                _i32, _vp, _vp, _vp]),
     "sglm_pn_update": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "sglm_group_cd_fits_per_wg": (_i32, [_i32]),
+    "sglm_group_bound": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "sglm_group_cd_shared": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                       _i32, C.c_double, _vp, _vp, _vp]),
 }
 
 

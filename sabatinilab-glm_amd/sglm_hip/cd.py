@@ -16,10 +16,11 @@ from . import engine as E
 CD_TOL = 1e-10
 
 
-def enet_batch(prob: E.Problem, objectives, reqs):
+def enet_batch(prob: E.Problem, objectives, reqs, groups=None):
     """Solve one ElasticNet fit per request; returns (FitResults, eta tensor [B][ld]).
     Grams and their centred float64 forms are formed once per distinct mask and shared
-    (sglm_hip.enet); X^T(m y) once per distinct (response, mask)."""
+    (sglm_hip.enet); X^T(m y) once per distinct (response, mask).  ``groups`` (a length-p
+    group-id sequence shared by the objectives): GroupLasso fits (sglm_hip.glasso)."""
     from . import enet
     d = prob.design
     B, P, ld, p = len(reqs), d.P, d.ld, d.p
@@ -31,7 +32,12 @@ def enet_batch(prob: E.Problem, objectives, reqs):
     fits = [{"mask": r.mask, "alpha": o.alpha, "l1_ratio": o.l1_ratio,
              "fit_intercept": r.fit_intercept, "max_iter": max(o.max_iter, 1)}
             for o, r in zip(objectives, reqs)]
-    w, b, sw, conv = enet.solve(prob, grams, fits, c, [ci[(r.resp, r.mask)] for r in reqs])
+    csr = None
+    if groups is not None:
+        from .glasso import group_csr
+        csr = group_csr(groups, p)
+    w, b, sw, conv = enet.solve(prob, grams, fits, c, [ci[(r.resp, r.mask)] for r in reqs],
+                                groups=csr)
     beta = np.zeros((B, P), dtype=np.float64)
     beta[:, :p] = w
     beta[:, p] = b
@@ -42,8 +48,8 @@ def enet_batch(prob: E.Problem, objectives, reqs):
     return res, bf.eta
 
 
-def enet_fit(prob, objectives, masks, resps, coef0=None):
+def enet_fit(prob, objectives, masks, resps, coef0=None, groups=None):
     reqs = [E.FitReq(E.FAM_SQUARED, 0.0, 0.0, m, r, o.fit_intercept, o.max_iter)
             for o, m, r in zip(objectives, masks, resps)]
-    res, _ = enet_batch(prob, objectives, reqs)
+    res, _ = enet_batch(prob, objectives, reqs, groups)
     return res

@@ -144,10 +144,10 @@ def xty(prob: E.Problem, pairs: Sequence[tuple]) -> torch.Tensor:
 
 
 def solve(prob: E.Problem, grams: SharedGrams, fits: Sequence[dict], c: torch.Tensor,
-          cidx: Sequence[int], stats: Optional[dict] = None):
+          cidx: Sequence[int], stats: Optional[dict] = None, groups=None):
     """ElasticNet per fit dict {mask, alpha, l1_ratio, fit_intercept, max_iter} with
     c[cidx[f]] = X^T(m y) of its (response, mask).  Returns (w [B][p] f64, b [B] f64,
-    sweeps [B] int, converged [B] bool) as host arrays."""
+    sweeps [B] int, converged [B] bool) as host arrays.  ``groups``: see solve_arrays."""
     p = prob.design.p
     if len(fits) == 0:
         return np.zeros((0, p)), np.zeros(0), np.zeros(0, int), np.zeros(0, bool)
@@ -155,15 +155,19 @@ def solve(prob: E.Problem, grams: SharedGrams, fits: Sequence[dict], c: torch.Te
         prob, grams, np.array([int(f["mask"]) for f in fits]),
         np.array([float(f["alpha"]) for f in fits]), np.array([float(f["l1_ratio"]) for f in fits]),
         np.array([bool(f["fit_intercept"]) for f in fits]),
-        max(int(f["max_iter"]) for f in fits), c, np.asarray(cidx), stats)
+        max(int(f["max_iter"]) for f in fits), c, np.asarray(cidx), stats, groups)
     return w.cpu().numpy(), b.cpu().numpy(), sw, conv
 
 
 def solve_arrays(prob: E.Problem, grams: SharedGrams, masks: np.ndarray, alpha: np.ndarray,
                  l1_ratio: np.ndarray, fit_intercept: np.ndarray, max_iter: int,
-                 c: torch.Tensor, cidx: np.ndarray, stats: Optional[dict] = None):
+                 c: torch.Tensor, cidx: np.ndarray, stats: Optional[dict] = None, groups=None):
     """solve() on per-fit arrays; returns (w [B][p], b [B]) as float64 DEVICE tensors and
-    (sweeps, converged) as host arrays."""
+    (sweeps, converged) as host arrays.
+
+    ``groups`` = (goff, gcols) (glasso.group_csr): the group lasso -- the L1 term becomes
+    alpha rho sum_g sqrt(k_g) |w_g|_2, solved by block descent (glasso.block_descent); the
+    Grams, the centring, q, the intercept and the stopping rule are the elastic net's."""
     d = prob.design
     p, dev = d.p, d.device
     B = int(masks.size)
@@ -203,7 +207,10 @@ def solve_arrays(prob: E.Problem, grams: SharedGrams, masks: np.ndarray, alpha: 
     if rec:                          # the roofline times the CD kernel alone (bench.py)
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    if fpw >= 2:
+    if groups is not None:
+        from . import glasso
+        glasso.block_descent(grams, p, qidx, alpha, q, l1, l2, groups, max_sweeps, CD_TOL, w, sw)
+    elif fpw >= 2:
         # fits sharing a Q go to the same workgroups, fpw at a time (padding slots -1);
         # within a Q, fits of equal alpha (other responses) share workgroups: a workgroup
         # sweeps until its last fit converges, and equal penalties converge alike (the
@@ -333,8 +340,9 @@ def _assemble(w, b, sw, conv, ss, yyh, cnt, c_pm, R: int, A: int, K: int,
 
 def cv_enet_path(X, Y, cv_idx, alphas: Sequence[float], l1_ratio: float = 0.5,
                  fit_intercept: bool = True, max_iter: int = 1000, score_method: str = "mse",
-                 stats: Optional[dict] = None, shard: bool = True):
-    """Multi-response elastic-net CV path.  Returns ``out[r][j]``: the result dict of
+                 stats: Optional[dict] = None, shard: bool = True, groups=None):
+    """Multi-response elastic-net CV path (with ``groups``, a length-p group-id array: the
+    multi-response group-lasso path, estimators.GroupLasso's objective per fit).  Returns ``out[r][j]``: the result dict of
     response r and alpha j with the keys of ``grid.run`` (cv_coefs p x K, cv_intercepts,
     cv_scores_train/test, cv_mean_score_train, cv_mean_score, cv_std_score, cv_R2_score,
     cv_mse_score, refit_coef, refit_intercept, n_iter, converged).
@@ -355,7 +363,7 @@ def cv_enet_path(X, Y, cv_idx, alphas: Sequence[float], l1_ratio: float = 0.5,
         if mine:
             st = {} if stats is not None else None
             res = cv_enet_path(X, Y[:, mine], cv_idx, alphas, l1_ratio, fit_intercept, max_iter,
-                               score_method, st, shard=False)
+                               score_method, st, shard=False, groups=groups)
             local = {r: v for r, v in zip(mine, res)}
             if stats is not None:
                 stats.update(st)
@@ -370,6 +378,12 @@ def cv_enet_path(X, Y, cv_idx, alphas: Sequence[float], l1_ratio: float = 0.5,
     if Y.shape[0] != n:
         raise ValueError(f"Y has {Y.shape[0]} rows, X has {n}")
     R, A, K = Y.shape[1], len(alphas), len(cv_idx)
+    csr = None
+    if groups is not None:
+        from .glasso import group_csr
+        csr = group_csr(groups, p)
+        if not 0.0 < float(l1_ratio) <= 1.0:
+            raise ValueError("group-lasso path: l1_ratio in (0, 1]")
     masks = []
     for tr, te in F.masks_from_cv_idx(cv_idx, n):
         masks += [tr, te]
@@ -411,7 +425,7 @@ def cv_enet_path(X, Y, cv_idx, alphas: Sequence[float], l1_ratio: float = 0.5,
     al = np.asarray(alphas, dtype=np.float64)[jj]
     w_d, b_d, sw, conv = solve_arrays(prob, grams, fmask, al, np.full(nfit, float(l1_ratio)),
                                       np.full(nfit, bool(fit_intercept)), int(max_iter), c,
-                                      rr * F_ + fmask, stats)
+                                      rr * F_ + fmask, stats, csr)
     pa = p + 1
     betad = torch.empty((nfit, pa), dtype=torch.float64, device=dev)
     betad[:, :p] = w_d

@@ -12,6 +12,8 @@ kwargs), and replace their numerics with the batched IRLS engine:
   TweedieRegressor  mean loss + alpha/2 ||w||^2                -> lam = alpha * n_train
                     (power 0 identity -> squared loss; power >= 1 log link -> Tweedie-log)
   Lasso/ElasticNet  1/(2n)||.||^2 + a rho |w|_1 + a(1-rho)/2 ||w||^2 -> Gram-space CD
+  GroupLasso        1/(2n)||.||^2 + a rho sum_g sqrt(k_g)|w_g|_2 + a(1-rho)/2 ||w||^2
+                    -> Gram-space block descent (glasso.py)
   TweedieRegressor(l1_ratio=rho > 0), log link:
                     mean loss + a rho |w|_1 + a(1-rho)/2 ||w||^2 -> proximal Newton (pn.py)
   BinomialRegressor mean [softplus(eta) - y eta] + alpha/2 ||w||^2, y in {0, 1}, logit link
@@ -35,6 +37,7 @@ class NotYetImplementedError(NotImplementedError):
 @dataclass
 class Objective:
     kind: str          # 'irls' | 'cd' | 'pn' (log link with an L1 term: pn.prox_newton)
+                       # | 'gcd' (group lasso: glasso block descent, ``groups`` set)
     family: int
     power: float
     alpha: float
@@ -43,6 +46,7 @@ class Objective:
     max_iter: int
     l1_ratio: float = 0.0
     tol: float = 1e-4
+    groups: tuple = None   # 'gcd': the group id of every column, as a tuple of ints
 
     def lam(self, n_train: float) -> float:
         return self.alpha * n_train if self.lam_scale == "n" else self.alpha
@@ -240,6 +244,9 @@ class _EngineRegressor:
         if obj.kind == "cd":
             from . import cd
             res = cd.enet_fit(prob, [obj], [0], [0], coef0=[c0])[0]
+        elif obj.kind == "gcd":
+            from . import cd
+            res = cd.enet_fit(prob, [obj], [0], [0], groups=obj.groups)[0]
         elif obj.kind == "pn":
             from . import pn
             nt = X.shape[0]
@@ -352,6 +359,46 @@ class Lasso(ElasticNet):
                          precompute=precompute, max_iter=max_iter, copy_X=copy_X, tol=tol,
                          warm_start=warm_start, positive=positive, random_state=random_state,
                          selection=selection)
+
+
+class GroupLasso(_EngineRegressor):
+    """Group lasso in sklearn ElasticNet's scaling,
+    1/(2n)|y - Xw - b|^2 + alpha rho sum_g sqrt(k_g) |w_g|_2 + alpha (1 - rho)/2 |w|^2 with
+    rho = l1_ratio in (0, 1]: ``groups`` gives one integer id per column, equal ids form a
+    group of k_g columns (the ids themselves are arbitrary), and a group's coefficients are
+    all in the model or all exactly zero.  With every column its own group this is ElasticNet;
+    ``alpha == 0`` is LinearRegression's objective.  No warm start along a path yet
+    (``warm_start`` is accepted and not used)."""
+    _params = ("alpha", "groups", "l1_ratio", "fit_intercept", "max_iter", "tol", "warm_start")
+
+    def __init__(self, alpha=1.0, *, groups, l1_ratio=1.0, fit_intercept=True, max_iter=1000,
+                 tol=1e-4, warm_start=False):
+        super().__init__(alpha=alpha, groups=groups, l1_ratio=l1_ratio,
+                         fit_intercept=fit_intercept, max_iter=max_iter, tol=tol,
+                         warm_start=warm_start)
+
+    def objective(self):
+        if np.ndim(self.alpha) or self.alpha < 0:
+            raise ValueError(f"The 'alpha' parameter of GroupLasso must be a float in the range "
+                             f"[0.0, inf). Got {self.alpha!r} instead.")
+        rho = float(self.l1_ratio)
+        if not 0.0 < rho <= 1.0:
+            raise ValueError(f"The 'l1_ratio' parameter of GroupLasso must be a float in the "
+                             f"range (0.0, 1.0]. Got {self.l1_ratio!r} instead.")
+        if self.alpha == 0:
+            return LinearRegression(fit_intercept=self.fit_intercept).objective()
+        ids = np.asarray(self.groups).reshape(-1)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise TypeError("groups: integer group ids, one per column")
+        return Objective("gcd", E.FAM_SQUARED, 0.0, float(self.alpha), "abs", self.fit_intercept,
+                         int(self.max_iter), rho, float(self.tol),
+                         groups=tuple(int(v) for v in ids))
+
+    def fit(self, X, y, sample_weight=None):
+        if self.alpha != 0 and np.asarray(self.groups).reshape(-1).shape[0] != _as2d(X).shape[1]:
+            raise ValueError(f"groups has {np.asarray(self.groups).reshape(-1).shape[0]} entries, "
+                             f"X has {_as2d(X).shape[1]} columns")
+        return super().fit(X, y, sample_weight)
 
 
 class TweedieRegressor(_EngineRegressor):

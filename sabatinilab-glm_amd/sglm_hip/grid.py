@@ -244,6 +244,9 @@ def check_drop_sets(drop_sets, p: int, groups=None):
                 if o.kind == "cd":
                     raise NotYetImplementedError("drop sets on the coordinate-descent path "
                                                  "(Lasso / ElasticNet objectives)")
+                if o.kind == "gcd":
+                    raise NotYetImplementedError("drop sets on the block-descent path "
+                                                 "(GroupLasso objectives)")
                 if o.family != E.FAM_SQUARED:
                     raise NotYetImplementedError("drop sets on the log-link IRLS path (Poisson "
                                                  "/ Gamma / Tweedie objectives)")
@@ -355,6 +358,9 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
         from .estimators import NotYetImplementedError
         raise NotYetImplementedError("row-sharded solve of elastic-net log-link objectives "
                                      "(Poisson / Gamma / Tweedie with l1_ratio > 0)")
+    if comm is not None and any(o.kind == "gcd" for g in groups for o in g["objectives"]):
+        from .estimators import NotYetImplementedError
+        raise NotYetImplementedError("row-sharded solve of group-lasso objectives (GroupLasso)")
     dsets = None
     if drop_sets is not None:
         dsets = check_drop_sets(drop_sets, X.p if isinstance(X, E.Design)
@@ -438,10 +444,18 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
 
     results = {}
     solve_groups = {}
+    groupings, grouping_of = [], {}          # distinct 'gcd' groupings; objective id -> index
     for i in mine:
         obj = objective(i)
-        key = (("cd", 0.0) if obj.kind == "cd" else ("pn", float(obj.power)) if obj.kind == "pn"
-               else (obj.family, float(obj.power)))
+        if obj.kind == "gcd":                # one solve per grouping (hashed once per objective)
+            if id(obj) not in grouping_of:
+                if obj.groups not in groupings:
+                    groupings.append(obj.groups)
+                grouping_of[id(obj)] = groupings.index(obj.groups)
+            key = ("gcd", grouping_of[id(obj)])
+        else:
+            key = (("cd", 0.0) if obj.kind == "cd" else ("pn", float(obj.power))
+                   if obj.kind == "pn" else (obj.family, float(obj.power)))
         solve_groups.setdefault(key, []).append(i)
     for key, idxs in solve_groups.items():
         reqs = []
@@ -463,9 +477,10 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
         t0 = tick("fit_table", t0)
         sets = np.array([[local[table[i][3]], local.get(table[i][5], -1)] for i in idxs],
                         dtype=np.int32)
-        if key[0] == "cd":
+        if key[0] in ("cd", "gcd"):
             from . import cd
-            res, eta = cd.enet_batch(prob, [objective(i) for i in idxs], reqs)
+            res, eta = cd.enet_batch(prob, [objective(i) for i in idxs], reqs,
+                                     groups=groupings[key[1]] if key[0] == "gcd" else None)
             sums = E.score_sums(prob, E.FAM_SQUARED, 0.0, eta, [table[i][4] for i in idxs],
                                 sets)
         elif key[0] == "pn":
