@@ -47,8 +47,17 @@ enum sglm_status { SGLM_OK = 0, SGLM_EINVAL = 1, SGLM_EHIP = 2, SGLM_ENOTPD = 3 
  *                       responses y in {0, 1} (the GLM 'Binomial' name); `power` is not read.
  *                       d loss/d eta = sigma(eta) - y, d2 loss/d eta2 = sigma (1 - sigma), both
  *                       from e = exp(-|eta|): finite for every finite eta, the weight >= 0.
- * Every entry that takes `family` accepts all three codes. */
-enum sglm_family { SGLM_FAM_SQUARED = 0, SGLM_FAM_TWEEDIE_LOG = 1, SGLM_FAM_BINOMIAL_LOGIT = 2 };
+ *  SGLM_FAM_NB2_LOG   : negative binomial NB2 with the log link and a fixed dispersion kappa > 0
+ *                       (Var y = mu + kappa mu^2), for responses y >= 0.  kappa travels in the
+ *                       `power` argument (a float in most entries: callers round kappa to float32
+ *                       once and use that value everywhere).  With z = eta + ln kappa:
+ *                         loss = (y + 1/kappa) softplus(z) - y eta,
+ *                         d loss/d eta = (mu - y) / (1 + kappa mu),
+ *                         d2 loss/d eta2 = mu (1 + kappa y) / (1 + kappa mu)^2 >= 0,
+ *                       from e = exp(-|z|): finite for every finite eta.  kappa -> 0 is Poisson.
+ * Every entry that takes `family` accepts all four codes. */
+enum sglm_family { SGLM_FAM_SQUARED = 0, SGLM_FAM_TWEEDIE_LOG = 1, SGLM_FAM_BINOMIAL_LOGIT = 2,
+                   SGLM_FAM_NB2_LOG = 3 };
 
 enum sglm_xtype { SGLM_X_BF16 = 0, SGLM_X_F32 = 1 };
 
@@ -125,7 +134,10 @@ int sglm_gemv_eta(const void* X, int32_t xtype, int64_t ld, int32_t P, int64_t n
  * W may be NULL: the weights are then not stored (eta, R and Rp are what they are with W
  * given); sglm_link_weights writes them later from the eta this call leaves behind.
  * family SGLM_FAM_BINOMIAL_LOGIT: R = M (sigma(eta) - y), W = M sigma (1 - sigma) as
- * e / (1 + e)^2 with e = exp(-|eta|) (no overflow, W >= 0; W underflows to 0 past |eta| ~ 87). */
+ * e / (1 + e)^2 with e = exp(-|eta|) (no overflow, W >= 0; W underflows to 0 past |eta| ~ 87).
+ * family SGLM_FAM_NB2_LOG (kappa = power): R = M (mu - y) / (1 + kappa mu), W = M mu (1 + kappa y)
+ * / (1 + kappa mu)^2, from e = exp(-|eta + ln kappa|) taken as kappa expf(eta) or expf(-eta) /
+ * kappa, whichever is <= 1: finite for every finite eta, W >= 0 for y >= 0. */
 int sglm_link_update(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                      const int32_t* slots, float* eta, const float* Y, const uint8_t* M,
                      const int32_t* fit_resp, const int32_t* fit_mask, float* W, float* R,
@@ -571,6 +583,16 @@ int sglm_mask_stats(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, i
                     int64_t n, const double* K, double power, double* out, void* work,
                     sglm_stream_t stream);
 
+/* NB2 saturated-constant sums: out[r][f] = sum_i M[f][i] c_kappa(Y[r][i]) (float64),
+ *   c_kappa(y) = y ln y - (y + 1/kappa) ln(1 + kappa y),  0 at y = 0,
+ * the constant that makes loss + c the NB2 unit deviance / 2 (>= 0, 0 at mu = y): the D^2 score
+ * of SGLM_FAM_NB2_LOG is 1 - (sum loss + sum c) / (null + sum c).  M, Y, F, R, n as
+ * sglm_mask_stats (which is not involved); kappa > 0; the sums two-level and in a fixed order.
+ * work: sglm_nb2_const_sums_work_bytes(F, R, n). */
+size_t sglm_nb2_const_sums_work_bytes(int32_t F, int32_t R, int64_t n);
+int sglm_nb2_const_sums(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, int32_t R,
+                        int64_t n, double kappa, double* out, void* work, sglm_stream_t stream);
+
 /* Line search: out[q][j] = sum_i M[m][i] * loss(y_i, eta_i + t[j] * deta_i) (float64),
  * for j < T, over fit slot k = slots[q] (q when slots is NULL), q < B.
  * `work`: sglm_rowsum_work_bytes(B, T, n).
@@ -587,6 +609,9 @@ int sglm_mask_stats(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, i
  * float64 losses and their differences instead: past it the f32 product loses the ratio to
  * cancellation (sigma -> 1, exp(deta) - 1 -> -1) and later overflows (0 * inf).  No finite input
  * gives NaN; with deta = 0 the five outputs are bitwise equal.
+ * NB2 (SGLM_FAM_NB2_LOG, kappa = power) with the same t: the Binomial identity times the row's
+ * factor, l(t) - l(0) = (y + 1/kappa) log1p(q (exp(t deta) - 1)) - y t deta with
+ * q = sigma(eta + ln kappa), the same |deta| > 3 guard, the same guarantees.
  * Every other (family, power, T, t) sums float64 losses per trial.
  * The sums are two-level and deterministic: block partials per 8192-row chunk, then one wave per
  * output sums the chunks in a fixed order. */
@@ -619,8 +644,8 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
  * With out == NULL and dmax == NULL the call is the link alone (undo, eta and Rp as above, no
  * sums; t, T and work are not read): what engine.irls enqueues behind the read-back of
  * sglm_loss_trials_max's sums, so that the link runs while the host decides the steps.
- * The contract holds for every family, SGLM_FAM_BINOMIAL_LOGIT and its difference branch
- * included.
+ * The contract holds for every family, SGLM_FAM_BINOMIAL_LOGIT and SGLM_FAM_NB2_LOG and their
+ * difference branches included.
  * SGLM_EINVAL on a null pointer (one of out / dmax alone included), T != 5 with sums, Bp < B or
  * Bp % 32, n outside 1..ld, ld % 256. */
 int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
@@ -656,7 +681,8 @@ int sglm_eta_pair_absmax(int64_t n, int64_t ld, int32_t npairs, const int32_t* p
  * set s in {0, 1} with mask sets[2k + s] (-1 = empty):
  *   out[k][s][0] = sum_i M * (y_i - mu_i)^2,  out[k][s][1] = sum_i M * loss(y_i, eta_i),
  * mu = inverse link(eta): eta, exp(eta), or sigma(eta) for SGLM_FAM_BINOMIAL_LOGIT (one
- * exponential per row shared by mu and the loss).  `work`: sglm_rowsum_work_bytes(B, 4, n). */
+ * exponential per row shared by mu and the loss); exp(eta) and the NB2 loss at kappa = power for
+ * SGLM_FAM_NB2_LOG.  `work`: sglm_rowsum_work_bytes(B, 4, n). */
 int sglm_score_sums(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                     const float* eta, const float* Y, const uint8_t* M,
                     const int32_t* fit_resp, const int32_t* sets, double* out, void* work,

@@ -149,6 +149,9 @@ __global__ void __launch_bounds__(256) eta_kernel(const TX* __restrict__ X, int6
 // plane (Bp rows per plane): the split is fused here instead of a separate pass over R.
 // W may be null: the IRLS loop reads W only where a Gram is formed from it and has
 // link_weights_kernel write those rows then, from the eta this kernel left behind.
+// NB2: the instantiation launched for SGLM_FAM_NB2_LOG (kappa in `power`); the other families
+// run the instantiation without that code.
+template <bool NB2>
 __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, int64_t n,
                                                    int64_t ld, const int32_t* __restrict__ slots,
                                                    float* __restrict__ eta,
@@ -161,6 +164,7 @@ __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, 
                                                    const float* __restrict__ step,
                                                    const float* __restrict__ deta,
                                                    const int32_t* __restrict__ rpos) {
+    if constexpr (NB2) family = SGLM_FAM_NB2_LOG;
     const int y = blockIdx.y;
     const int k = slots ? slots[y] : y;
     const int ry = rpos ? rpos[y] : y;          // packed-R row of this fit (< 0: none)
@@ -185,7 +189,7 @@ __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, 
             }
             const float mi = (float)m[i];
             if (mi != 0.0f) {
-                const LossOut o = half_loss(family, power, yv[i], ei);
+                const LossOut o = half_loss<true, NB2>(family, power, yv[i], ei);
                 wi = mi * o.h;
                 ri = mi * o.g;
             }
@@ -204,11 +208,13 @@ __global__ void __launch_bounds__(256) link_kernel(int32_t family, float power, 
 
 // W[k][i] of link_kernel alone (k = slots[y], all slots when slots is null), from the same
 // expression on the same eta: bitwise the weights that kernel writes.
+template <bool NB2>
 __global__ void __launch_bounds__(256) link_weights_kernel(
     int32_t family, float power, int64_t n, int64_t ld, const int32_t* __restrict__ slots,
     const float* __restrict__ eta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
     const int32_t* __restrict__ fit_resp, const int32_t* __restrict__ fit_mask,
     float* __restrict__ W) {
+    if constexpr (NB2) family = SGLM_FAM_NB2_LOG;
     const int y = blockIdx.y;
     const int k = slots ? slots[y] : y;
     const float* e = eta + (int64_t)k * ld;
@@ -221,7 +227,7 @@ __global__ void __launch_bounds__(256) link_weights_kernel(
         if (i < n) {
             const float mi = (float)m[i];
             if (mi != 0.0f) {
-                const LossOut o = half_loss(family, power, yv[i], e[i]);
+                const LossOut o = half_loss<true, NB2>(family, power, yv[i], e[i]);
                 wi = mi * o.h;
             }
         }
@@ -368,9 +374,49 @@ __device__ __forceinline__ LogitTrials logit_trials_row(float yi, float ei, floa
     return o;
 }
 
-// LOGIT: the instantiation launched for SGLM_FAM_BINOMIAL_LOGIT (the other families run the
-// code they always ran).
-template <bool LOGIT>
+// NB2 (log link, dispersion kappa) with the same step lengths, one row, in the same layout.
+// With z = eta + ln kappa and q = sigma(z), (1 + kappa e^(eta + s)) / (1 + kappa e^eta) =
+// 1 + q (e^s - 1), so
+//   l(t) - l(0) = (y + 1/kappa) log1p(q x(t)) - y t d,   x(t) = exp(t d) - 1:
+// the Binomial identity times the per-row factor y + 1/kappa, which multiplies the term and its
+// error alike, so that family's guard (|d| > kLogitDiffMaxD: float64 losses and their
+// differences) and its argument carry over unchanged.  q comes from e = exp(-|z|) as nb2_loss
+// forms it, l(0) = (y + 1/kappa)(max(z, 0) + log1p(e)) - y eta.
+__device__ __forceinline__ LogitTrials nb2_trials_row(float kappa, float yi, float ei, float di) {
+    const double yd = (double)yi * (double)di;
+    LogitTrials o;
+    if (fabsf(di) <= kLogitDiffMaxD) {
+        const float ik = 1.0f / kappa;
+        const float z = ei + logf(kappa);
+        const float e = z <= 0.0f ? kappa * expf(ei) : expf(-ei) * ik;
+        const float inv = 1.0f / (1.0f + e);
+        const float q = z <= 0.0f ? e * inv : inv;
+        const double f = (double)(yi + ik);
+        const float x8 = expm1f(0.125f * di);
+        const float x4 = x8 * (2.0f + x8), x2 = x4 * (2.0f + x4), x1 = x2 * (2.0f + x2);
+        o.l0 = f * ((double)fmaxf(z, 0.0f) + (double)log1pf(e)) - (double)yi * (double)ei;
+        o.d1 = f * (double)log1pf(q * x1) - yd;
+        o.d2 = f * (double)log1pf(q * x2) - 0.5 * yd;
+        o.d4 = f * (double)log1pf(q * x4) - 0.25 * yd;
+        o.d8 = f * (double)log1pf(q * x8) - 0.125 * yd;
+    } else {
+        const double z = ei, dd = di, yy = yi, kp = kappa;
+        o.l0 = nb2_loss_d(kp, yy, z);
+        o.d1 = nb2_loss_d(kp, yy, z + dd) - o.l0;
+        o.d2 = nb2_loss_d(kp, yy, z + 0.5 * dd) - o.l0;
+        o.d4 = nb2_loss_d(kp, yy, z + 0.25 * dd) - o.l0;
+        o.d8 = nb2_loss_d(kp, yy, z + 0.125 * dd) - o.l0;
+    }
+    return o;
+}
+
+// FK: 0 for the kernels of the families SGLM_FAM_SQUARED / SGLM_FAM_TWEEDIE_LOG (the code they
+// always ran), SGLM_FAM_BINOMIAL_LOGIT or SGLM_FAM_NB2_LOG for the instantiation launched for
+// that family alone.
+static int family_kind(int32_t family) {
+    return family == SGLM_FAM_BINOMIAL_LOGIT || family == SGLM_FAM_NB2_LOG ? family : 0;
+}
+template <int FK>
 __global__ void __launch_bounds__(256) loss_trials_kernel(
     int32_t family, float power, int64_t n, int64_t ld, const float* __restrict__ eta,
     const float* __restrict__ deta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
@@ -379,7 +425,9 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
     float* __restrict__ dmax, const int32_t* __restrict__ slots) {
     __shared__ double sh[4];
     __shared__ float shm[4];
-    if constexpr (LOGIT) family = SGLM_FAM_BINOMIAL_LOGIT;
+    constexpr bool LOGIT = FK == SGLM_FAM_BINOMIAL_LOGIT, NB2 = FK == SGLM_FAM_NB2_LOG;
+    constexpr bool SPEC = LOGIT || NB2;      // one family: static trial indices, no dispatch
+    if constexpr (SPEC) family = FK;
     const int q = blockIdx.y;                       // output row
     const int k = slots ? slots[q] : q;             // fit slot
     const int32_t nchunks = gridDim.x;
@@ -399,14 +447,15 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
     // (no cancellation): two f32 transcendentals per row, the terms and sums in float64.
     // acc[0] holds L(0), acc[j >= 1] the difference; the block's partial of trial j is their sum.
     // Binomial: the same layout from logit_trials_row.
-    const bool halving = (LOGIT || (family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f)) && T == 5 &&
+    const bool halving = (SPEC || (family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f)) && T == 5 &&
                          tv[0] == 0.0f && tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f &&
                          tv[4] == 0.125f;
     if (halving) {
         auto row = [&](double mi, float yi, float ei, float di) __attribute__((always_inline)) {
             mx = fmaxf(mx, fabsf(di));
-            if constexpr (LOGIT) {
-                const LogitTrials o = logit_trials_row(yi, ei, di);
+            if constexpr (SPEC) {
+                const LogitTrials o = NB2 ? nb2_trials_row(power, yi, ei, di)
+                                          : logit_trials_row(yi, ei, di);
                 acc[0] += mi * o.l0; acc[1] += mi * o.d1; acc[2] += mi * o.d2;
                 acc[3] += mi * o.d4; acc[4] += mi * o.d8;
                 return;
@@ -448,13 +497,13 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
             if (mi == 0.0) continue;
             const double yi = y[i], ei = e[i], di = d[i];
             mx = fmaxf(mx, fabsf((float)di));
-            if constexpr (LOGIT) {
+            if constexpr (SPEC) {
                 // static indices: acc stays in registers next to the float64 log1p / exp
 #pragma unroll
                 for (int j = 0; j < kMaxTrials; ++j)
                     if (j < T)
-                        acc[j] += mi * half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yi,
-                                                   ei + (double)tv[j] * di);
+                        acc[j] += mi * half_loss_d<LOGIT, NB2>(FK, (double)power, yi,
+                                                               ei + (double)tv[j] * di);
             } else {
                 for (int j = 0; j < T; ++j)
                     acc[j] += mi * half_loss_d<false>(family, (double)power, yi,
@@ -469,7 +518,7 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
         else if (halving) s += s0;
         if (threadIdx.x == 0) part[((int64_t)q * T + j) * nchunks + blockIdx.x] = s;
     };
-    if constexpr (LOGIT) {
+    if constexpr (SPEC) {
 #pragma unroll
         for (int j = 0; j < kMaxTrials; ++j)
             if (j < T) put(j, acc[j]);
@@ -498,7 +547,7 @@ __global__ void __launch_bounds__(256) loss_trials_kernel(
 //    (the last chunk's block writes those).
 // A quad of four masked-out rows skips only the losses.
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-template <bool LOSS, bool LOGIT>
+template <bool LOSS, int FK>
 __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     int32_t family, float power, int64_t n, int64_t ld, float* __restrict__ eta,
     const float* __restrict__ deta, const float* __restrict__ Y, const uint8_t* __restrict__ M,
@@ -508,7 +557,9 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     __bf16* __restrict__ Rp, int32_t Bp) {
     __shared__ double sh[4];
     __shared__ float shm[4];
-    if constexpr (LOGIT) family = SGLM_FAM_BINOMIAL_LOGIT;
+    constexpr bool LOGIT = FK == SGLM_FAM_BINOMIAL_LOGIT, NB2 = FK == SGLM_FAM_NB2_LOG;
+    constexpr bool SPEC = LOGIT || NB2;      // one family: static trial indices, no dispatch
+    if constexpr (SPEC) family = FK;
     const int q = blockIdx.y;                       // output row = packed R row = undo row
     const int k = slots ? slots[q] : q;             // fit slot
     const int32_t nchunks = gridDim.x;
@@ -526,7 +577,7 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     const int64_t i1 = min(i0 + kRowChunk, n);
     // R of one row from the updated predictor, as link_kernel forms it
     auto link_row = [&](float mf, float yi, float en) {
-        const LossOut o = half_loss<LOGIT>(family, power, yi, en);
+        const LossOut o = half_loss<LOGIT, NB2>(family, power, yi, en);
         return mf * o.g;
     };
     auto store_r = [&](int64_t i, float ri) {
@@ -539,14 +590,15 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
     // LOSS = false: the link alone (no sums, tv / part / dmax not touched), four rows at a time
     bool halving = !LOSS;
     if constexpr (LOSS)
-        halving = (LOGIT || (family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f)) && T == 5 &&
+        halving = (SPEC || (family == SGLM_FAM_TWEEDIE_LOG && power == 1.0f)) && T == 5 &&
                   tv[0] == 0.0f && tv[1] == 1.0f && tv[2] == 0.5f && tv[3] == 0.25f &&
                   tv[4] == 0.125f;
     if (halving) {
         auto row = [&](double mi, float yi, float ei, float di) __attribute__((always_inline)) {
             mx = fmaxf(mx, fabsf(di));
-            if constexpr (LOGIT) {
-                const LogitTrials o = logit_trials_row(yi, ei, di);
+            if constexpr (SPEC) {
+                const LogitTrials o = NB2 ? nb2_trials_row(power, yi, ei, di)
+                                          : logit_trials_row(yi, ei, di);
                 acc[0] += mi * o.l0; acc[1] += mi * o.d1; acc[2] += mi * o.d2;
                 acc[3] += mi * o.d4; acc[4] += mi * o.d8;
                 return;
@@ -636,12 +688,12 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
                 const float yr = y[i];
                 const double yi = yr, ei = eo, di = dr;
                 mx = fmaxf(mx, fabsf((float)di));
-                if constexpr (LOGIT) {
+                if constexpr (SPEC) {
 #pragma unroll
                     for (int j = 0; j < kMaxTrials; ++j)
                         if (j < T)
-                            acc[j] += mi * half_loss_d(SGLM_FAM_BINOMIAL_LOGIT, 0.0, yi,
-                                                       ei + (double)tv[j] * di);
+                            acc[j] += mi * half_loss_d<LOGIT, NB2>(FK, (double)power, yi,
+                                                                   ei + (double)tv[j] * di);
                 } else {
                     for (int j = 0; j < T; ++j)
                         acc[j] += mi * half_loss_d<false>(family, (double)power, yi,
@@ -662,7 +714,7 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
         else if (halving) s += s0;
         if (threadIdx.x == 0) part[((int64_t)q * T + j) * nchunks + blockIdx.x] = s;
     };
-    if constexpr (LOGIT) {
+    if constexpr (SPEC) {
 #pragma unroll
         for (int j = 0; j < kMaxTrials; ++j)
             if (j < T) put(j, acc[j]);
@@ -677,13 +729,14 @@ __global__ void __launch_bounds__(256) loss_trials_link_kernel(
                   __float_as_uint(fmaxf(fmaxf(shm[0], shm[1]), fmaxf(shm[2], shm[3]))));
 }
 
-template <bool LOGIT>
+template <int FK>
 __global__ void __launch_bounds__(256) score_kernel(
     int32_t family, float power, int64_t n, int64_t ld, const float* __restrict__ eta,
     const float* __restrict__ Y, const uint8_t* __restrict__ M,
     const int32_t* __restrict__ fit_resp, const int32_t* __restrict__ sets,
     double* __restrict__ part) {
     __shared__ double sh[4];
+    constexpr bool LOGIT = FK == SGLM_FAM_BINOMIAL_LOGIT, NB2 = FK == SGLM_FAM_NB2_LOG;
     const int k = blockIdx.y;
     const int32_t nchunks = gridDim.x;
     const float* e = eta + (int64_t)k * ld;
@@ -707,6 +760,9 @@ __global__ void __launch_bounds__(256) score_kernel(
             const double ex = exp(-fabs(ei));
             mu = ei >= 0.0 ? 1.0 / (1.0 + ex) : ex / (1.0 + ex);
             l = fmax(ei, 0.0) + log1p(ex) - yi * ei;
+        } else if constexpr (NB2) {
+            mu = exp(ei);
+            l = nb2_loss_d((double)power, yi, ei);
         } else {
             mu = inv_link_d<false>(family, ei);
             l = pois ? mu - yi * ei : half_loss_d<false>(family, (double)power, yi, ei);
@@ -906,6 +962,32 @@ __global__ void __launch_bounds__(256) mask_stats_kernel(const uint8_t* __restri
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mn;
     __syncthreads();
     if (threadIdx.x == 0) out[(kStat - 1) * nch] = fmin(fmin(sh[0], sh[1]), fmin(sh[2], sh[3]));
+}
+
+// sum m c_kappa(y) per (mask f, response r), c the NB2 saturated constant
+//   c_kappa(y) = y ln y - (y + 1/kappa) ln(1 + kappa y)   (0 at y = 0),
+// so that loss + c >= 0 with equality at mu = y: the deviance of the D^2 score.  Block partials
+// per 8192-row chunk, then reduce_chunks_d's fixed-order sum, as mask_stats_kernel.
+__global__ void __launch_bounds__(256) nb2_const_kernel(const uint8_t* __restrict__ M,
+                                                        const double* __restrict__ Y, int64_t n,
+                                                        int64_t ldm, int32_t F, double kappa,
+                                                        double* __restrict__ part) {
+    __shared__ double sh[4];
+    const int f = blockIdx.y, r = blockIdx.z;
+    const uint8_t* m = M + (int64_t)f * ldm;
+    const double* y = Y + (int64_t)r * n;
+    const double ik = 1.0 / kappa;
+    double a = 0.0;
+    const int64_t i0 = (int64_t)blockIdx.x * kRowChunk;
+    const int64_t i1 = min(i0 + kRowChunk, n);
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+        const double w = (double)m[i];
+        if (w == 0.0) continue;
+        const double yi = y[i];
+        if (yi > 0.0) a += w * (yi * log(yi) - (yi + ik) * log1p(kappa * yi));
+    }
+    const double v = block_sum_d(a, sh);
+    if (threadIdx.x == 0) part[((int64_t)r * F + f) * gridDim.x + blockIdx.x] = v;
 }
 
 __global__ void __launch_bounds__(256) mask_stats_reduce(const double* __restrict__ part,
@@ -1316,9 +1398,15 @@ int sglm_link_update(int32_t family, float power, int64_t n, int64_t ld, int32_t
     if (B <= 0) return SGLM_OK;
     if (!eta || !Y || !M || !fit_resp || !fit_mask || (!R && !Rp)) { set_error("sglm_link_update: null pointer"); return SGLM_EINVAL; }
     dim3 grid(grid1(ld, 256, 1024), (unsigned)B);
-    link_kernel<<<grid, 256, 0, as_stream(stream)>>>(family, power, n, ld, slots, eta, Y, M,
-                                                     fit_resp, fit_mask, W, R, (__bf16*)Rp,
-                                                     (B + 31) / 32 * 32, step, deta, nullptr);
+    const int32_t Bp = (B + 31) / 32 * 32;
+    if (family == SGLM_FAM_NB2_LOG)
+        link_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(
+            family, power, n, ld, slots, eta, Y, M, fit_resp, fit_mask, W, R, (__bf16*)Rp, Bp,
+            step, deta, nullptr);
+    else
+        link_kernel<false><<<grid, 256, 0, as_stream(stream)>>>(
+            family, power, n, ld, slots, eta, Y, M, fit_resp, fit_mask, W, R, (__bf16*)Rp, Bp,
+            step, deta, nullptr);
     return check_launch("link_kernel");
 }
 
@@ -1334,9 +1422,14 @@ int sglm_link_update_rp(int32_t family, float power, int64_t n, int64_t ld, int3
         return SGLM_EINVAL;
     }
     dim3 grid(grid1(ld, 256, 1024), (unsigned)B);
-    link_kernel<<<grid, 256, 0, as_stream(stream)>>>(family, power, n, ld, slots, eta, Y, M,
-                                                     fit_resp, fit_mask, W, R, (__bf16*)Rp, Bp,
-                                                     step, deta, rpos);
+    if (family == SGLM_FAM_NB2_LOG)
+        link_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(
+            family, power, n, ld, slots, eta, Y, M, fit_resp, fit_mask, W, R, (__bf16*)Rp, Bp,
+            step, deta, rpos);
+    else
+        link_kernel<false><<<grid, 256, 0, as_stream(stream)>>>(
+            family, power, n, ld, slots, eta, Y, M, fit_resp, fit_mask, W, R, (__bf16*)Rp, Bp,
+            step, deta, rpos);
     return check_launch("link_kernel");
 }
 
@@ -1350,8 +1443,12 @@ int sglm_link_weights(int32_t family, float power, int64_t n, int64_t ld, int32_
         return SGLM_EINVAL;
     }
     dim3 grid(grid1(ld, 256, 1024), (unsigned)B);
-    link_weights_kernel<<<grid, 256, 0, as_stream(stream)>>>(family, power, n, ld, slots, eta, Y,
-                                                             M, fit_resp, fit_mask, W);
+    if (family == SGLM_FAM_NB2_LOG)
+        link_weights_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(
+            family, power, n, ld, slots, eta, Y, M, fit_resp, fit_mask, W);
+    else
+        link_weights_kernel<false><<<grid, 256, 0, as_stream(stream)>>>(
+            family, power, n, ld, slots, eta, Y, M, fit_resp, fit_mask, W);
     return check_launch("link_weights_kernel");
 }
 
@@ -1395,10 +1492,17 @@ int sglm_loss_trials(int32_t family, float power, int64_t n, int64_t ld, int32_t
     (void)ld;
     const int32_t nc = row_chunks(n);
     hipStream_t s = as_stream(stream);
-    if (family == SGLM_FAM_BINOMIAL_LOGIT)
-        loss_trials_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
-    else
-        loss_trials_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
+    const dim3 grid((unsigned)nc, (unsigned)B);
+    switch (family_kind(family)) {
+    case SGLM_FAM_BINOMIAL_LOGIT:
+        loss_trials_kernel<SGLM_FAM_BINOMIAL_LOGIT><<<grid, 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
+        break;
+    case SGLM_FAM_NB2_LOG:
+        loss_trials_kernel<SGLM_FAM_NB2_LOG><<<grid, 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
+        break;
+    default:
+        loss_trials_kernel<0><<<grid, 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, nullptr, slots);
+    }
     int st = check_launch("loss_trials_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
@@ -1421,10 +1525,17 @@ int sglm_loss_trials_max(int32_t family, float power, int64_t n, int64_t ld, int
         set_error("sglm_loss_trials_max: hipMemsetAsync failed");
         return SGLM_EHIP;
     }
-    if (family == SGLM_FAM_BINOMIAL_LOGIT)
-        loss_trials_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
-    else
-        loss_trials_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
+    const dim3 grid((unsigned)nc, (unsigned)B);
+    switch (family_kind(family)) {
+    case SGLM_FAM_BINOMIAL_LOGIT:
+        loss_trials_kernel<SGLM_FAM_BINOMIAL_LOGIT><<<grid, 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
+        break;
+    case SGLM_FAM_NB2_LOG:
+        loss_trials_kernel<SGLM_FAM_NB2_LOG><<<grid, 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
+        break;
+    default:
+        loss_trials_kernel<0><<<grid, 256, 0, s>>>(family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax, slots);
+    }
     int st = check_launch("loss_trials_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * T;
@@ -1447,15 +1558,19 @@ int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, in
     }
     const int32_t nc = row_chunks(n);
     hipStream_t s = as_stream(stream);
-    const bool logit = family == SGLM_FAM_BINOMIAL_LOGIT;
+    const int fk = family_kind(family);
     const dim3 grid((unsigned)nc, (unsigned)B);
     if (link_only) {
-        if (logit)
-            loss_trials_link_kernel<false, true><<<grid, 256, 0, s>>>(
+        if (fk == SGLM_FAM_BINOMIAL_LOGIT)
+            loss_trials_link_kernel<false, SGLM_FAM_BINOMIAL_LOGIT><<<grid, 256, 0, s>>>(
+                family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
+                nullptr, slots, undo, (__bf16*)Rp, Bp);
+        else if (fk == SGLM_FAM_NB2_LOG)
+            loss_trials_link_kernel<false, SGLM_FAM_NB2_LOG><<<grid, 256, 0, s>>>(
                 family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
                 nullptr, slots, undo, (__bf16*)Rp, Bp);
         else
-            loss_trials_link_kernel<false, false><<<grid, 256, 0, s>>>(
+            loss_trials_link_kernel<false, 0><<<grid, 256, 0, s>>>(
                 family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, nullptr, 0, nullptr,
                 nullptr, slots, undo, (__bf16*)Rp, Bp);
         return check_launch("loss_trials_link_kernel<link only>");
@@ -1464,12 +1579,16 @@ int sglm_loss_trials_link(int32_t family, float power, int64_t n, int64_t ld, in
         set_error("sglm_loss_trials_link: hipMemsetAsync failed");
         return SGLM_EHIP;
     }
-    if (logit)
-        loss_trials_link_kernel<true, true><<<grid, 256, 0, s>>>(
+    if (fk == SGLM_FAM_BINOMIAL_LOGIT)
+        loss_trials_link_kernel<true, SGLM_FAM_BINOMIAL_LOGIT><<<grid, 256, 0, s>>>(
+            family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
+            slots, undo, (__bf16*)Rp, Bp);
+    else if (fk == SGLM_FAM_NB2_LOG)
+        loss_trials_link_kernel<true, SGLM_FAM_NB2_LOG><<<grid, 256, 0, s>>>(
             family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
             slots, undo, (__bf16*)Rp, Bp);
     else
-        loss_trials_link_kernel<true, false><<<grid, 256, 0, s>>>(
+        loss_trials_link_kernel<true, 0><<<grid, 256, 0, s>>>(
             family, power, n, ld, eta, deta, Y, M, fit_resp, fit_mask, t, T, (double*)work, dmax,
             slots, undo, (__bf16*)Rp, Bp);
     int st = check_launch("loss_trials_link_kernel");
@@ -1605,6 +1724,28 @@ int sglm_mask_stats(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, i
     return check_launch("mask_stats_reduce");
 }
 
+size_t sglm_nb2_const_sums_work_bytes(int32_t F, int32_t R, int64_t n) {
+    return (size_t)F * R * row_chunks(n) * sizeof(double);
+}
+
+int sglm_nb2_const_sums(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, int32_t R,
+                        int64_t n, double kappa, double* out, void* work, sglm_stream_t stream) {
+    if (F <= 0 || R <= 0) return SGLM_OK;
+    if (!M || !Y || !out || !work || ldm < n || n <= 0 || !(kappa > 0.0)) {
+        set_error("sglm_nb2_const_sums: bad args");
+        return SGLM_EINVAL;
+    }
+    hipStream_t s = as_stream(stream);
+    const int32_t nc = row_chunks(n);
+    nb2_const_kernel<<<dim3((unsigned)nc, (unsigned)F, (unsigned)R), 256, 0, s>>>(
+        M, Y, n, ldm, F, kappa, (double*)work);
+    int st = check_launch("nb2_const_kernel");
+    if (st) return st;
+    const int64_t rows = (int64_t)R * F;
+    reduce_chunks_d<<<reduce_grid(rows), 256, 0, s>>>((const double*)work, rows, nc, out);
+    return check_launch("reduce_chunks_d");
+}
+
 int sglm_score_sums(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
                     const float* eta, const float* Y, const uint8_t* M,
                     const int32_t* fit_resp, const int32_t* sets, double* out, void* work,
@@ -1613,10 +1754,13 @@ int sglm_score_sums(int32_t family, float power, int64_t n, int64_t ld, int32_t 
     if (!eta || !Y || !M || !fit_resp || !sets || !out || !work) { set_error("sglm_score_sums: null pointer"); return SGLM_EINVAL; }
     const int32_t nc = row_chunks(n);
     hipStream_t s = as_stream(stream);
+    const dim3 grid((unsigned)nc, (unsigned)B);
     if (family == SGLM_FAM_BINOMIAL_LOGIT)
-        score_kernel<true><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
+        score_kernel<SGLM_FAM_BINOMIAL_LOGIT><<<grid, 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
+    else if (family == SGLM_FAM_NB2_LOG)
+        score_kernel<SGLM_FAM_NB2_LOG><<<grid, 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
     else
-        score_kernel<false><<<dim3((unsigned)nc, (unsigned)B), 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
+        score_kernel<0><<<grid, 256, 0, s>>>(family, power, n, ld, eta, Y, M, fit_resp, sets, (double*)work);
     int st = check_launch("score_kernel");
     if (st) return st;
     const int64_t rows = (int64_t)B * 4;

@@ -31,12 +31,52 @@ __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) {
 // from e = exp(-|eta|) in (0, 1]: no overflow at any finite eta, h = sigma (1 - sigma) >= 0.
 // LOGIT = false leaves the family-2 code out: kernels instantiated for the families 0 / 1 alone
 // (the trial-loss and score passes) keep the registers and occupancy they had without it.
+// family 3: negative binomial NB2, log link, dispersion kappa in the `power` slot:
+//   l = (y + 1/kappa) softplus(z) - y eta,  z = eta + ln kappa  (nb2_loss below).
+// NB2 = true adds the family-3 branch; the default leaves it out, so every instantiation of the
+// families 0 / 1 / 2 is the code it was before the family existed.
 struct LossOut { float loss, g, h; };
 
-template <bool LOGIT = true>
+// NB2, one row, single precision.  With mu = exp(eta), e = exp(-|z|) = kappa mu (z <= 0) or
+// 1 / (kappa mu) (z > 0), q = sigma(z):
+//   g = (y + 1/kappa) q - y       = (mu - y) / (1 + e)           z <= 0
+//                                 = (1/kappa - y e) / (1 + e)    z >  0
+//   h = (y + 1/kappa) q (1 - q)   = (y + 1/kappa) e / (1 + e)^2  >= 0 for y >= 0.
+// e comes from expf(+-eta) scaled by kappa, not from the rounded sum z: its relative error is
+// expf's own at every |eta|, and the side z falls on matters only near z = 0, where both forms
+// agree.  No overflow at any finite eta (the exponential taken is the one <= 1 / kappa or <= kappa).
+__device__ __forceinline__ LossOut nb2_loss(float kappa, float y, float eta) {
+    LossOut o;
+    const float ik = 1.0f / kappa;
+    const float z = eta + logf(kappa);
+    float e, num;
+    if (z <= 0.0f) {
+        const float mu = expf(eta);
+        e = kappa * mu;
+        num = mu - y;
+    } else {
+        e = expf(-eta) * ik;
+        num = ik - y * e;
+    }
+    const float inv = 1.0f / (1.0f + e);
+    o.loss = (y + ik) * (fmaxf(z, 0.0f) + log1pf(e)) - y * eta;
+    o.g = num * inv;
+    o.h = (y + ik) * e * inv * inv;
+    return o;
+}
+
+// NB2 loss in double precision: (y + 1/kappa) softplus(eta + ln kappa) - y eta
+__device__ __forceinline__ double nb2_loss_d(double kappa, double y, double eta) {
+    const double z = eta + log(kappa);
+    return (y + 1.0 / kappa) * (fmax(z, 0.0) + log1p(exp(-fabs(z)))) - y * eta;
+}
+
+template <bool LOGIT = true, bool NB2 = false>
 __device__ __forceinline__ LossOut half_loss(int family, float power, float y, float eta) {
     LossOut o;
-    if (family == SGLM_FAM_SQUARED) {
+    if (NB2 && family == SGLM_FAM_NB2_LOG) {
+        o = nb2_loss(power, y, eta);
+    } else if (family == SGLM_FAM_SQUARED) {
         float r = eta - y;
         o.loss = 0.5f * r * r; o.g = r; o.h = 1.0f;
     } else if (LOGIT && family == SGLM_FAM_BINOMIAL_LOGIT) {
@@ -63,8 +103,9 @@ __device__ __forceinline__ LossOut half_loss(int family, float power, float y, f
 }
 
 // double-precision loss for reductions that decide line searches / scores
-template <bool LOGIT = true>
+template <bool LOGIT = true, bool NB2 = false>
 __device__ __forceinline__ double half_loss_d(int family, double power, double y, double eta) {
+    if (NB2 && family == SGLM_FAM_NB2_LOG) return nb2_loss_d(power, y, eta);
     if (family == SGLM_FAM_SQUARED) { double r = eta - y; return 0.5 * r * r; }
     if (LOGIT && family == SGLM_FAM_BINOMIAL_LOGIT)
         return fmax(eta, 0.0) + log1p(exp(-fabs(eta))) - y * eta;
@@ -73,8 +114,9 @@ __device__ __forceinline__ double half_loss_d(int family, double power, double y
     return exp((2.0 - power) * eta) / (2.0 - power) - y * exp((1.0 - power) * eta) / (1.0 - power);
 }
 
-template <bool LOGIT = true>
+template <bool LOGIT = true, bool NB2 = false>
 __device__ __forceinline__ double inv_link_d(int family, double eta) {
+    if (NB2 && family == SGLM_FAM_NB2_LOG) return exp(eta);                // log link
     if (LOGIT && family == SGLM_FAM_BINOMIAL_LOGIT) {        // the logistic function, no overflow
         const double e = exp(-fabs(eta));
         return eta >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);

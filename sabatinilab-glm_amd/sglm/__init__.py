@@ -13,7 +13,12 @@ Behaviour fixed on purpose (SURVEY.md §7 "Reference defects"), API unchanged:
   * ``NotYetImplementedError`` is defined (the reference raises an undefined name).
 ``'Binomial'`` (which the reference lists but never implemented) is the Bernoulli GLM with the
 logit link in the Tweedie families' mean-scaled objective (``BinomialRegressor``); responses are
-exactly 0 or 1, ``predict`` returns the probability.  Logistic/Multinomial (sklearn's
+exactly 0 or 1, ``predict`` returns the probability.  ``'NegativeBinomial'`` / ``'NB2'`` (not a
+reference name) is the negative binomial with the log link and a fixed dispersion,
+``GLM('NegativeBinomial', alpha=a, kappa=k)`` (``NegativeBinomialRegressor``: Var y = mu +
+kappa mu^2, kappa rounded to float32 once, responses >= 0, ``predict`` returns the mean, ``'r2'``
+is D^2); kappa is a hyperparameter, elastic-net / group penalties and drop sets on it are not
+implemented.  Logistic/Multinomial (sklearn's
 ``LogisticRegression`` surface) and the PCA warm-start are out of scope.
 """
 from __future__ import annotations
@@ -26,7 +31,8 @@ import pandas as pd
 import scipy.stats
 
 from sglm_hip.estimators import (BinomialRegressor, ElasticNet, GroupLasso, Lasso,  # noqa: F401
-                                 LinearRegression, LogisticRegression, NotYetImplementedError,
+                                 LinearRegression, LogisticRegression,
+                                 NegativeBinomialRegressor, NotYetImplementedError,
                                  PoissonRegressor, Ridge, TweedieRegressor, host_matrix)
 
 
@@ -76,6 +82,8 @@ class GLM():
             Base = TweedieRegressor
         elif model_name in {'Binomial'}:
             Base = BinomialRegressor
+        elif model_name in {'NegativeBinomial', 'NB2'}:
+            Base = NegativeBinomialRegressor
         elif model_name in {'Logistic', 'Multinomial'}:
             kwargs['multi_class'] = 'multinomial' if model_name == 'Multinomial' else 'auto'
             kwargs['n_jobs'] = kwargs['n_jobs'] if 'n_jobs' in kwargs else -1

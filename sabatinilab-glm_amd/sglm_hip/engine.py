@@ -44,6 +44,7 @@ except ImportError as e:  # pragma: no cover - torch is part of the image
 FAM_SQUARED = 0
 FAM_TWEEDIE_LOG = 1
 FAM_BINOMIAL_LOGIT = 2         # HalfBinomialLoss, logit link, y in {0, 1} (power not read)
+FAM_NB2_LOG = 3                # negative binomial NB2, log link, y >= 0; `power` carries kappa
 X_BF16, X_F32 = 0, 1
 COL_PAD = 256
 ROW_PAD = 256
@@ -54,6 +55,11 @@ ARMIJO_SIGMA = 2.0 ** -11      # sklearn _newton_solver.py:214
 # 1e-6, 5.1e-6 at 1e-5), 30x inside the full-size test's 1e-5 and 300x inside the north star's
 # Poisson 1e-4, for 590 -> 580 fit-iterations (C4 28.92 -> 28.31 ms; profiles/r06b_stop_tol.json)
 STOP_TOL = float(__import__("os").environ.get("SGLM_STOP_TOL", "3e-6"))
+# NB2 fits stop at STOP_TOL * NB2_STOP_FACTOR: on over-dispersed counts the 'mse' score moves by
+# about 7 x the coefficient distance (residuals y - mu of several mu), so the 3e-7 max|coef| that
+# STOP_TOL leaves shows as 2e-6 in a fold's score; at a tenth of it the distance is 1e-8 .. 6e-8
+# (tests/test_gpu_nb2.py) for about one more Newton iteration per fit
+NB2_STOP_FACTOR = 0.1
 STOP_SCALE_FLOOR = float(__import__("os").environ.get("SGLM_STOP_SCALE_FLOOR", "0.1"))
 # round-2 rule, for comparison runs: max|t d| <= tol * (1 + max|w|), intercept included
 STOP_LEGACY = __import__("os").environ.get("SGLM_STOP_RULE", "") == "legacy"
@@ -1725,9 +1731,11 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     require_gpu()
     if not reqs:
         return [], None
-    tol = STOP_TOL if tol is None else float(tol)
     d = prob.design
     fam, power = reqs[0].family, float(reqs[0].power)
+    if tol is None:
+        tol = STOP_TOL * (NB2_STOP_FACTOR if fam == FAM_NB2_LOG else 1.0)
+    tol = float(tol)
     if any(r.family != fam or float(r.power) != power for r in reqs):
         raise ValueError("irls(): one loss family per batch")
     if any(r.drop >= 0 for r in reqs):
@@ -1740,7 +1748,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     dev = d.device
     bf = (bufs or _scratch().buf).get(B0, P, ld, dev)
     st = _stream()
-    log_link = fam == FAM_TWEEDIE_LOG
+    log_link = fam in (FAM_TWEEDIE_LOG, FAM_NB2_LOG)
     reqs0 = list(reqs)
 
     # the per-fit penalty rows, start coefficients and index arrays are built on the device from
@@ -1804,7 +1812,9 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     const_hess = fam == FAM_SQUARED
     # drift divisor c of the weight bound e^(c D): |2 - power| for the log link; the logit
     # weight has d ln h / d eta = 1 - 2 mu in (-1, 1), so c = 1 as for Poisson
-    drift_c = 1.0 if fam == FAM_BINOMIAL_LOGIT else max(1.0, abs(2.0 - power))
+    # (NB2: d ln h / d eta = 1 - 2 sigma(eta + ln kappa), the same bound; power is kappa there)
+    drift_c = (1.0 if fam in (FAM_BINOMIAL_LOGIT, FAM_NB2_LOG)
+               else max(1.0, abs(2.0 - power)))
     reuse_tol = 0.0 if const_hess else HESS_REUSE_TOL / drift_c
     share_tol = 0.0 if const_hess else min(HESS_SHARE_TOL / drift_c, reuse_tol)
     # Device state is held per SLOT (one per fit, fixed for the whole solve); every per-fit
@@ -1871,7 +1881,7 @@ def irls(prob: Problem, reqs: List[FitReq], tol: Optional[float] = None,
     all_rows = np.array([mall[int(r.mask)] for r in reqs])
     # the weight m * h(y, eta) is one constant on such a mask only when h does not depend on y:
     # the Poisson log link (h = exp(eta)) and the logit link (h = mu (1 - mu)); Gamma /
-    # Tweedie's h carries y on every row
+    # Tweedie's h carries y on every row, and so does NB2's (mu (1 + kappa y) / (1 + kappa mu)^2)
     use_lag_gram = (LAG_GRAM and ((fam == FAM_TWEEDIE_LOG and power == 1.0)
                                   or fam == FAM_BINOMIAL_LOGIT) and d.lag is not None
                     and getattr(d.lag, "ebits", None) is not None
@@ -3379,7 +3389,7 @@ def _partition(reqs: List[FitReq], ngroups: int, rows=None) -> List[List[int]]:
     sharing); with fewer masks than groups the largest mask's fits are dealt alternately in
     penalty order."""
     if (rows is not None and HESS_XMASK_TOL > 0
-            and reqs[0].family in (FAM_TWEEDIE_LOG, FAM_BINOMIAL_LOGIT)):
+            and reqs[0].family in (FAM_TWEEDIE_LOG, FAM_BINOMIAL_LOGIT, FAM_NB2_LOG)):
         fams = {}
         for i, r in enumerate(reqs):
             fams.setdefault(_family_key(r, rows[i]) or ("solo", i), []).append(i)

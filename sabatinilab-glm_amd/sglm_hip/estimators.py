@@ -19,6 +19,10 @@ kwargs), and replace their numerics with the batched IRLS engine:
   BinomialRegressor mean [softplus(eta) - y eta] + alpha/2 ||w||^2, y in {0, 1}, logit link
                     (sklearn's HalfBinomialLoss in the TweedieRegressor objective; the GLM
                     'Binomial' name) -> lam = alpha * n_train
+  NegativeBinomialRegressor
+                    mean [(y + 1/kappa) log(1 + kappa e^eta) - y eta] + alpha/2 ||w||^2, y >= 0,
+                    log link, fixed dispersion kappa (NB2; the GLM 'NegativeBinomial' / 'NB2'
+                    names) -> lam = alpha * n_train
 """
 from __future__ import annotations
 
@@ -235,7 +239,9 @@ class _EngineRegressor:
         if X.shape[0] != y.shape[0]:
             raise ValueError(f"Found input variables with inconsistent numbers of samples: "
                              f"[{X.shape[0]}, {y.shape[0]}]")
-        _check_y_range(obj.power if obj.family == E.FAM_TWEEDIE_LOG else 0, y)
+        # (NB2 takes Poisson's range: y >= 0)
+        _check_y_range(obj.power if obj.family == E.FAM_TWEEDIE_LOG
+                       else 1 if obj.family == E.FAM_NB2_LOG else 0, y)
         d = self._design(Xh)
         prob = E.Problem(d, [y], [np.ones(X.shape[0], np.uint8)])
         c0, b0 = self._warm()
@@ -285,7 +291,7 @@ class _EngineRegressor:
         obj = self.objective()
         if obj.family == E.FAM_BINOMIAL_LOGIT:
             return sigmoid_np(eta)
-        return np.exp(eta) if obj.family == E.FAM_TWEEDIE_LOG else eta
+        return np.exp(eta) if obj.family in (E.FAM_TWEEDIE_LOG, E.FAM_NB2_LOG) else eta
 
     def score(self, X, y, sample_weight=None):
         """R^2 (Gaussian estimators, sklearn RegressorMixin.score)."""
@@ -514,6 +520,68 @@ class BinomialRegressor(_EngineRegressor):
         return 1.0 - dev / dev0 if dev0 > 0 else (1.0 if dev == 0 else 0.0)
 
 
+def nb2_kappa(kappa) -> float:
+    """The dispersion every layer uses: ``kappa`` rounded to float32 once (the C ABI carries it in
+    the float ``power`` argument of the row passes), as a Python float.  The kernels, the host
+    scores, the null deviance and the saturated constant all take this one value."""
+    k = float(kappa)
+    if not (math.isfinite(k) and k > 0.0):
+        raise ValueError(f"kappa must be a finite float > 0. Got {kappa!r} instead.")
+    with np.errstate(over="ignore", under="ignore"):
+        k32 = float(np.float32(k))
+    if not (math.isfinite(k32) and k32 > 0.0 and math.isfinite(1.0 / k32)):
+        raise ValueError(f"kappa = {kappa!r} is outside the float32 range")
+    return k32
+
+
+class NegativeBinomialRegressor(_EngineRegressor):
+    """Negative-binomial GLM (NB2: Var y = mu + kappa mu^2) with the log link and a fixed
+    dispersion ``kappa > 0``, in TweedieRegressor's mean-scaled objective,
+    mean_i [(y_i + 1/kappa) log(1 + kappa e^eta_i) - y_i eta_i] + alpha/2 |w|^2 (unpenalised
+    intercept): statsmodels' ``NegativeBinomial(alpha=kappa)`` family, pyglmnet's
+    ``'neg-binomial'`` with a fixed theta.  kappa -> 0 is PoissonRegressor.  Responses are >= 0
+    (non-integers accepted, as for Poisson).
+
+    ``kappa`` is rounded to float32 once (``nb2_kappa``: the C ABI carries it in a float) and
+    that value is the dispersion of the fit, of ``score`` and of the grid's scores;
+    ``get_params`` returns what was given.  kappa is a hyperparameter: it is not estimated.
+    Elastic-net and group penalties, drop sets and a log-likelihood score are not implemented."""
+    _params = ("kappa", "alpha", "fit_intercept", "solver", "max_iter", "tol", "warm_start",
+               "verbose", "l1_ratio")
+
+    def __init__(self, *, kappa=1.0, alpha=1.0, fit_intercept=True, solver="lbfgs", max_iter=100,
+                 tol=1e-4, warm_start=False, verbose=0, l1_ratio=0.0):
+        super().__init__(kappa=kappa, alpha=alpha, fit_intercept=fit_intercept, solver=solver,
+                         max_iter=max_iter, tol=tol, warm_start=warm_start, verbose=verbose,
+                         l1_ratio=l1_ratio)
+
+    def objective(self):
+        kappa = nb2_kappa(self.kappa)
+        if self.alpha < 0:
+            raise ValueError("alpha must be >= 0")
+        rho = float(self.l1_ratio)
+        if not 0.0 <= rho <= 1.0:
+            raise ValueError(f"The 'l1_ratio' parameter of {type(self).__name__} must be a float "
+                             f"in the range [0.0, 1.0]. Got {self.l1_ratio!r} instead.")
+        if rho > 0.0 and self.alpha > 0:
+            raise NotYetImplementedError("NegativeBinomialRegressor(l1_ratio > 0): elastic-net "
+                                         "penalties on the NB2 family")
+        return Objective("irls", E.FAM_NB2_LOG, kappa, float(self.alpha), "n",
+                         self.fit_intercept, int(self.max_iter))
+
+    def score(self, X, y, sample_weight=None):
+        """D^2, the fraction of NB2 deviance explained at the fit's kappa:
+        1 - (sum loss + sum c) / (null + sum c), c the saturated constant."""
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        _check_y_range(1, y)
+        kappa = nb2_kappa(self.kappa)
+        dev = float(np.sum(nb2_loss_np(kappa, y, self._linear_predictor(X))))
+        const = float(np.sum(nb2_constant_np(kappa, y)))
+        dev0 = nb2_null_np(kappa, float(y.size), float(y.sum()))
+        den = dev0 + const
+        return 1.0 - (dev + const) / den if den > 0 else (1.0 if dev + const <= 0 else 0.0)
+
+
 class LogisticRegression:
     """Out of scope: the reference's Logistic/Multinomial path."""
 
@@ -548,6 +616,31 @@ def binomial_null_np(cnt: float, ym: float) -> float:
     if not 0.0 < ym < 1.0:
         return 0.0
     return -cnt * (ym * math.log(ym) + (1.0 - ym) * math.log1p(-ym))
+
+
+def nb2_loss_np(kappa, y, eta):
+    """Host float64 NB2 loss (y + 1/kappa) softplus(eta + ln kappa) - y eta (log link): the
+    negative log-likelihood up to terms free of eta.  For scores only."""
+    z = eta + math.log(kappa)
+    return (y + 1.0 / kappa) * (np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))) - y * eta
+
+
+def nb2_constant_np(kappa, y):
+    """The NB2 saturated constant c(y) = y ln y - (y + 1/kappa) ln(1 + kappa y), 0 at y = 0:
+    loss + c >= 0, 0 at mu = y."""
+    y = np.asarray(y, dtype=np.float64)
+    pos = y > 0
+    ys = np.where(pos, y, 1.0)
+    return np.where(pos, ys * np.log(ys) - (ys + 1.0 / kappa) * np.log1p(kappa * ys), 0.0)
+
+
+def nb2_null_np(kappa: float, cnt: float, sy: float) -> float:
+    """Summed NB2 loss of ``cnt`` rows with sum ``sy`` at the null optimum eta = log(mean y), in
+    closed form: (sy + cnt/kappa) log(1 + kappa ybar) - sy log ybar (0 rows or ybar = 0: 0)."""
+    if cnt <= 0 or sy <= 0:
+        return 0.0
+    ym = sy / cnt
+    return (sy + cnt / kappa) * math.log1p(kappa * ym) - sy * math.log(ym)
 
 
 def loss_constant_np(power, y):

@@ -35,7 +35,9 @@ class _MaskStats:
     """float64 statistics of every (response, mask) pair that the scores and the y-range check
     need: count, mean, sum of squares about the mean, min y; per Tweedie power the summed
     loss constant and null deviance (``power="binomial"``: constant 0 for 0/1 labels, the null
-    deviance in closed form from the counts, no device pass).  One pass of sglm_mask_stats over
+    deviance in closed form from the counts, no device pass; ``power=("nb2", kappa)``: the NB2
+    saturated-constant sums from one pass of sglm_nb2_const_sums per kappa, the null deviance in
+    closed form from the mask's count and sum).  One pass of sglm_mask_stats over
     the device masks and responses per power (the reference computes them per fold on host copies,
     backend/sglm.py:150-184, 388-408)."""
 
@@ -90,6 +92,29 @@ class _MaskStats:
             self._const[power] = self._pass(float(power))[:, :, 3].T      # F x R
         return self._const[power]
 
+    def _nb2_consts(self, kappa):
+        """Summed NB2 saturated constant of each (mask, response) for one dispersion."""
+        key = ("nb2", kappa)
+        if key not in self._const:
+            torch, _lib, prob = self.torch, self._lib, self.prob
+            work = torch.empty(_lib.query("sglm_nb2_const_sums_work_bytes", self.F, self.R,
+                                          self.n), dtype=torch.uint8, device=self.Yd.device)
+            out = torch.empty((self.R, self.F), dtype=torch.float64, device=self.Yd.device)
+            _lib.call("sglm_nb2_const_sums", prob.M.data_ptr(), prob.M.shape[1], self.F,
+                      self.Yd.data_ptr(), self.R, self.n, float(kappa), out.data_ptr(),
+                      work.data_ptr(), E._stream())
+            if self.comm is not None:
+                self.comm.sum_(out)                      # the constants add over the slabs
+            self._const[key] = out.cpu().numpy().T       # F x R
+        return self._const[key]
+
+    def all_zero(self, r, m) -> bool:
+        """Whether response r is 0 on every row of mask m: min y == 0 (exact) and the sum within
+        the rounding of the centred sums it is rebuilt from (cnt terms of size |K|)."""
+        cnt = float(self.cnt[m])
+        return bool(cnt and self.ymin[m, r] == 0.0 and float(self.sy[m, r])
+                    <= 64 * np.finfo(np.float64).eps * abs(float(self.K[r])) * cnt)
+
     def get(self, r, m, power=None):
         key = (r, m, power)
         if key in self.c:
@@ -103,6 +128,12 @@ class _MaskStats:
                 out["const"] = 0.0
                 # the number of ones is an integer: exact from the rounded sum
                 out["null"] = binomial_null_np(cnt, round(float(self.sy[m, r])) / cnt)
+        elif isinstance(power, tuple):               # ("nb2", kappa)
+            if cnt:
+                from .estimators import nb2_null_np
+                out["const"] = float(self._nb2_consts(power[1])[m, r])
+                out["null"] = (nb2_null_np(power[1], cnt, float(self.sy[m, r]))
+                               if ym > 0 and not self.all_zero(r, m) else np.inf)
         elif power is not None and cnt:
             out["const"] = float(self._consts(power)[m, r])
             sy = float(self.sy[m, r])
@@ -302,7 +333,8 @@ def rank_share(plan, groups: Sequence[dict], rank: int, world: int):
         units.setdefault((t[0], t[1]), []).append(i)
     fam = (world > 1 and SHARD_PLAN == "mask_major" and E.HESS_XMASK_TOL > 0
            and len(units) >= world
-           and all(o.kind == "irls" and o.family in (E.FAM_TWEEDIE_LOG, E.FAM_BINOMIAL_LOGIT)
+           and all(o.kind == "irls" and o.family in (E.FAM_TWEEDIE_LOG, E.FAM_BINOMIAL_LOGIT,
+                                                     E.FAM_NB2_LOG)
                    for g in groups for o in g["objectives"]))
     if fam:
         # whole parameters (a penalty's split fits + refit: one cross-mask family, solved on
@@ -422,6 +454,10 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
         if fam_i == E.FAM_TWEEDIE_LOG:
             st_ = ms.get(r, local[m])
             bad = max(bad, int(bool(st_["cnt"]) and (st_["ymin"] < 0 or st_["mean"] <= 0)))
+        elif fam_i == E.FAM_NB2_LOG:             # Poisson's range (y >= 0) and verdict; a fold of
+            st_ = ms.get(r, local[m])            # zeros is told from the rounding of its sum
+            bad = max(bad, int(bool(st_["cnt"]) and (st_["ymin"] < 0 or st_["mean"] <= 0
+                                                     or ms.all_zero(r, local[m]))))
         elif fam_i == E.FAM_BINOMIAL_LOGIT:
             st_ = ms.get(r, local[m])
             ones = round(st_["mean"] * st_["cnt"])       # the centred sums carry rounding
@@ -497,7 +533,8 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
             _, _, k, m, r, mt = table[i]
             obj = objective(i)
             pw = (obj.power if obj.family == E.FAM_TWEEDIE_LOG
-                  else "binomial" if obj.family == E.FAM_BINOMIAL_LOGIT else None)
+                  else "binomial" if obj.family == E.FAM_BINOMIAL_LOGIT
+                  else ("nb2", float(obj.power)) if obj.family == E.FAM_NB2_LOG else None)
             sc = {}
             if k < 0:
                 if mt >= 0:

@@ -7,7 +7,10 @@ the first ``L-1`` and last ``L`` rows of the expansion hold the NaN fill and are
 ``N_raw = N + 2L - 1`` leaves exactly ``N`` rows.  ``beta_true ~ N(0, 0.1^2)`` (rng 1);
 Poisson ``y ~ Poisson(exp(X beta + b))`` with ``b = -1`` (rng 2); Gaussian
 ``y = X beta + 0.5 + N(0, 1)``; Binomial ``y ~ Bernoulli(sigma(X beta + b))`` (rng 2, one uniform
-draw per row).  Trial ids ``t // 100``.
+draw per row); NB2 (``family="nb2"``, ``kappa``) ``y ~ Poisson(mu g)`` with
+``g ~ Gamma(shape 1/kappa, scale kappa)`` (rng 2: the Gamma draws, then the Poisson draws), so
+that E y = mu and Var y = mu + kappa mu^2, default ``b = -1`` as for Poisson.  Trial ids
+``t // 100``.
 
 The linear predictor is computed by per-event convolution of E with the lag kernel, so the
 1M x 2000 design never has to exist on the host.
@@ -49,14 +52,15 @@ def shift_list(L):
     return [0] + list(range(-L, 0)) + list(range(1, L))
 
 
-def make(N, m, L, family="poisson", rho=0.02, seed=0, beta_scale=0.1, intercept=None):
+def make(N, m, L, family="poisson", rho=0.02, seed=0, beta_scale=0.1, intercept=None,
+         kappa=1.0):
     rng = np.random.default_rng(seed)
     N_raw = N + 2 * L - 1
     E = (rng.random((N_raw, m)) < rho).astype(np.float32)
     shifts = shift_list(L)
     p = len(shifts) * m
     beta = np.random.default_rng(seed + 1).normal(0.0, beta_scale, size=p)
-    b = (-1.0 if family == "poisson" else 0.5) if intercept is None else intercept
+    b = (-1.0 if family in ("poisson", "nb2") else 0.5) if intercept is None else intercept
     # eta[t] = sum_{shift s, event a} E[t + r0 - s, a] * beta[s, a]  (r0 = L-1)
     eta = np.full(N, b, dtype=np.float64)
     r0 = L - 1
@@ -69,6 +73,11 @@ def make(N, m, L, family="poisson", rho=0.02, seed=0, beta_scale=0.1, intercept=
     elif family == "gamma":
         mu = np.exp(eta)
         y = rng2.gamma(2.0, mu / 2.0)
+    elif family == "nb2":
+        if not kappa > 0:
+            raise ValueError("synth.make(family='nb2'): kappa > 0")
+        g = rng2.gamma(1.0 / kappa, kappa, size=N)       # Gamma-Poisson mixture, E g = 1
+        y = rng2.poisson(np.exp(eta) * g).astype(np.float64)
     elif family == "binomial":
         y = (rng2.random(N) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
     else:
