@@ -593,6 +593,43 @@ size_t sglm_nb2_const_sums_work_bytes(int32_t F, int32_t R, int64_t n);
 int sglm_nb2_const_sums(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, int32_t R,
                         int64_t n, double kappa, double* out, void* work, sglm_stream_t stream);
 
+/* Integer histogram of every (mask, response) pair (nb2ml.hip):
+ *   hist[r][f][v] = sum_i M[f][i] [Y[r][i] == v]   (uint64 [R][F][nbins], zeroed by the call),
+ * M, ldm, F, Y, R, n as sglm_mask_stats.  flags[r][f] (int32, zeroed by the call) gets bit 0
+ * when a row with M > 0 holds a y that is negative, not an integer, NaN or >= nbins; such a row
+ * is not counted.  The y-only terms of the count likelihoods are host sums over the tail
+ * T[j] = sum_{v > j} hist[v]: sum m S(y, k) = sum_j T[j] log1p(k j), sum m lgamma(y + 1) =
+ * sum_j T[j] ln(j + 1), exact for every kappa.  Integer adds only (a per-workgroup LDS histogram
+ * for the bins below 1024, global atomics above and for the flush): the result does not depend
+ * on the order, and a repeated call is bitwise equal.  No work buffer.
+ * SGLM_EINVAL on a null pointer, ldm < n, n <= 0 or nbins <= 0. */
+int sglm_count_hist(const uint8_t* M, int64_t ldm, int32_t F, const double* Y, int32_t R,
+                    int64_t n, int64_t nbins, uint64_t* hist, int32_t* flags,
+                    sglm_stream_t stream);
+
+/* The eta-dependent sums of the NB2 log-likelihood and of its derivatives in kappa at fixed
+ * predictors (nb2ml.hip), for K <= 8 dispersions per fit from one exp per row.  Launch row
+ * f < nfit reads fit slot slots[f] (f when slots is NULL) of eta (f32 [*][ld]); Y, M, fit_resp,
+ * fit_mask as sglm_score_sums / sglm_loss_trials take them (indexed by launch row); kappa is
+ * double [nfit][K], every value > 0.  With mu = exp(eta), x = kappa mu, r = mu / (1 + x) and
+ * g(x) = (log1p(x) - x / (1 + x)) / x^2 = 1/2 - 2x/3 + 3x^2/4 - ...:
+ *   out[f][k][0] = sum m (y eta - (y + 1/kappa) log1p(x)),
+ *   out[f][k][1] = sum m (mu^2 g(x) - y r)              d out[0] / d kappa,
+ *   out[f][k][2] = sum m (mu^3 g'(x) + y r^2)           d out[1] / d kappa (steers a search),
+ * float64 from the f32 eta.  g and g' are a 20-term series below x = 1/8; above it mu^2 g is
+ * (log1p(x) - x / (1 + x)) / kappa^2 and mu^3 g' is (r^2 - 2 mu^2 g) / kappa, so that no power
+ * of mu is formed: every output is finite for |eta| <= 200 and kappa in [2^-20, 2^10].  The form
+ * log1p(x) / kappa^2 - (y + 1/kappa) r of out[1] cancels terms of size mu / kappa and is not
+ * used.  Rows with m = 0 are not read.  The sums are two-level and in a fixed order (block
+ * partials per 8192-row chunk, then one wave per output over the chunks): a repeated call is
+ * bitwise equal.  work: sglm_nb2_kappa_sums_work_bytes(nfit, K, n).
+ * SGLM_EINVAL on a null pointer (slots excepted), n outside 1..ld, ld % 4, K outside 1..8. */
+size_t sglm_nb2_kappa_sums_work_bytes(int32_t nfit, int32_t K, int64_t n);
+int sglm_nb2_kappa_sums(int64_t n, int64_t ld, int32_t nfit, const int32_t* slots,
+                        const float* eta, const float* Y, const uint8_t* M,
+                        const int32_t* fit_resp, const int32_t* fit_mask, const double* kappa,
+                        int32_t K, double* out, void* work, sglm_stream_t stream);
+
 /* Line search: out[q][j] = sum_i M[m][i] * loss(y_i, eta_i + t[j] * deta_i) (float64),
  * for j < T, over fit slot k = slots[q] (q when slots is NULL), q < B.
  * `work`: sglm_rowsum_work_bytes(B, T, n).

@@ -17,8 +17,10 @@ exactly 0 or 1, ``predict`` returns the probability.  ``'NegativeBinomial'`` / `
 reference name) is the negative binomial with the log link and a fixed dispersion,
 ``GLM('NegativeBinomial', alpha=a, kappa=k)`` (``NegativeBinomialRegressor``: Var y = mu +
 kappa mu^2, kappa rounded to float32 once, responses >= 0, ``predict`` returns the mean, ``'r2'``
-is D^2); kappa is a hyperparameter, elastic-net / group penalties and drop sets on it are not
-implemented.  Logistic/Multinomial (sklearn's
+is D^2); ``kappa='ml'`` estimates the dispersion by maximum likelihood (``kappa_``), elastic-net /
+group penalties and drop sets on the family are not implemented.  ``score_method='ll'`` is the
+mean log-likelihood per scored row (Poisson, NB2, Binomial; integer counts), the score that can
+choose ``kappa`` on a grid and compare Poisson with NB2.  Logistic/Multinomial (sklearn's
 ``LogisticRegression`` surface) and the PCA warm-start are out of scope.
 """
 from __future__ import annotations
@@ -107,6 +109,9 @@ class GLM():
 
         if score_method == 'r2':
             self.score = self.r2_score
+        elif score_method == 'll':
+            self._ll_family()                      # refuses Normal / Gamma / other Tweedie powers
+            self.score = self.ll_score
         else:
             self.score = self.neg_mse_score
 
@@ -119,6 +124,34 @@ class GLM():
     def r2_score(self, X, y):
         """backend/sglm.py:169-184 (R^2 for Gaussian estimators, D^2 for Tweedie)."""
         return self.model.score(X, y)
+
+    def _ll_family(self):
+        """(engine family code, Tweedie power) of a family with a log-likelihood score."""
+        from sglm_hip import engine as E, nb2
+        if self.model_name in {'NegativeBinomial', 'NB2'}:
+            return E.FAM_NB2_LOG, 0.0
+        if self.model_name == 'Binomial':
+            return E.FAM_BINOMIAL_LOGIT, 0.0
+        if self.Base is TweedieRegressor and float(self.kwargs.get('power', 0.0)) == 1.0:
+            return E.FAM_TWEEDIE_LOG, 1.0
+        raise NotYetImplementedError(
+            f"score_method='ll' / log-likelihood on the {self.model_name} family"
+            + (f" (power={self.kwargs.get('power', 0.0)})" if self.model_name == 'Tweedie' else "")
+            + ": the count log-likelihoods cover Poisson, NB2 and Binomial")
+
+    def ll_score(self, X, y):
+        """Mean log-likelihood per row at the fitted coefficients (host float64 from the
+        engine's linear predictor; NB2 at the model's ``kappa`` / ``kappa_``)."""
+        from sglm_hip import engine as E, nb2
+        fam, _ = self._ll_family()
+        if type(X) == pd.DataFrame:
+            X = host_matrix(X)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if nb2.needs_counts(fam):
+            nb2.check_counts(y)                    # integer counts, before any device work
+        eta = self.model._linear_predictor(X)
+        kappa = self.model._kappa() if fam == E.FAM_NB2_LOG else None
+        return nb2.loglik_np(fam, y, eta, kappa) / y.shape[0]
 
     def pca_fit(self, X, y):
         """backend/sglm.py:186-223 — PCA warm start; its only reference use is discarded
@@ -182,12 +215,27 @@ class GLM():
         return self.model.predict(X)          # a lagged frame (sglm_hip.lagframe) stays resident
 
     def log_likelihood(self, prediction, truth) -> float:
-        """backend/sglm.py:349-385 (Gaussian only, as in the reference)."""
+        """backend/sglm.py:349-385 for the Gaussian case; the summed log-likelihood of Poisson,
+        NB2 (at the model's ``kappa`` / ``kappa_``) and Binomial predictions (the mean, or the
+        probability) in host float64, from the cancellation-free sums of sglm_hip.nb2."""
         if self.model_name in {'Normal', 'Gaussian'}:
             resid = truth - prediction
             std = np.std(resid)
             return np.sum(scipy.stats.norm.logpdf(resid, loc=0, scale=std))
-        raise NotYetImplementedError(self.model_name)
+        from sglm_hip import engine as E, nb2
+        try:
+            fam, _ = self._ll_family()
+        except NotYetImplementedError:
+            raise NotYetImplementedError(self.model_name) from None
+        pred = np.asarray(prediction, dtype=np.float64).reshape(-1)
+        truth = np.asarray(truth, dtype=np.float64).reshape(-1)
+        with np.errstate(divide='ignore'):
+            if fam == E.FAM_BINOMIAL_LOGIT:
+                eta = np.log(pred) - np.log1p(-pred)
+            else:
+                eta = np.log(pred)
+        kappa = self.model._kappa() if fam == E.FAM_NB2_LOG else None
+        return nb2.loglik_np(fam, truth, eta, kappa)
 
 
 def calc_R2(residuals: np.ndarray, mean_residuals: np.ndarray) -> float:

@@ -117,7 +117,7 @@ def cv_glm_mult_params(X, y, cv_idx, model_name, glm_kwarg_lst, verbose=0, score
             best_score_std = cv_result['cv_std_score']
             best_params = cv_result['glm_kwargs']
             best_model = cv_result['model']
-        elif score_method == 'mse' and cv_result['cv_mean_score'] > best_score:
+        elif score_method in ('mse', 'll') and cv_result['cv_mean_score'] > best_score:
             best_score = cv_result['cv_mean_score']
             best_score_std = cv_result['cv_std_score']
             best_params = cv_result['glm_kwargs']

@@ -118,6 +118,10 @@ SIGNATURES = {
                                   _vp]),
     "sglm_nb2_const_sums_work_bytes": (_sz, [_i32, _i32, _i64]),
     "sglm_nb2_const_sums": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i64, C.c_double, _vp, _vp, _vp]),
+    "sglm_count_hist": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),
+    "sglm_nb2_kappa_sums_work_bytes": (_sz, [_i32, _i32, _i64]),
+    "sglm_nb2_kappa_sums": (C.c_int, [_i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                      _vp, _vp, _vp]),
     "sglm_rowsum_work_bytes": (_sz, [_i32, _i32, _i64]),
     "sglm_loss_trials": (C.c_int, [_i32, _f32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _i32, _vp, _vp, _vp]),

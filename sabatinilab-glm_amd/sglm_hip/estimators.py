@@ -21,8 +21,9 @@ kwargs), and replace their numerics with the batched IRLS engine:
                     'Binomial' name) -> lam = alpha * n_train
   NegativeBinomialRegressor
                     mean [(y + 1/kappa) log(1 + kappa e^eta) - y eta] + alpha/2 ||w||^2, y >= 0,
-                    log link, fixed dispersion kappa (NB2; the GLM 'NegativeBinomial' / 'NB2'
-                    names) -> lam = alpha * n_train
+                    log link, dispersion kappa fixed or estimated by maximum likelihood
+                    (kappa='ml', nb2.py) (NB2; the GLM 'NegativeBinomial' / 'NB2' names)
+                    -> lam = alpha * n_train
 """
 from __future__ import annotations
 
@@ -205,6 +206,11 @@ class _EngineRegressor:
     def objective(self) -> Objective:  # pragma: no cover - abstract
         raise NotImplementedError
 
+    def _objective(self) -> Objective:
+        """The objective fit / predict use (NegativeBinomialRegressor(kappa='ml') has one only
+        once fitted: at ``kappa_``)."""
+        return self.objective()
+
     def _warm(self):
         if getattr(self, "warm_start", False) and hasattr(self, "coef_"):
             c = np.asarray(self.coef_, dtype=np.float64).reshape(-1)
@@ -288,7 +294,7 @@ class _EngineRegressor:
 
     def predict(self, X):
         eta = self._linear_predictor(X)
-        obj = self.objective()
+        obj = self._objective()
         if obj.family == E.FAM_BINOMIAL_LOGIT:
             return sigmoid_np(eta)
         return np.exp(eta) if obj.family in (E.FAM_TWEEDIE_LOG, E.FAM_NB2_LOG) else eta
@@ -544,8 +550,22 @@ class NegativeBinomialRegressor(_EngineRegressor):
 
     ``kappa`` is rounded to float32 once (``nb2_kappa``: the C ABI carries it in a float) and
     that value is the dispersion of the fit, of ``score`` and of the grid's scores;
-    ``get_params`` returns what was given.  kappa is a hyperparameter: it is not estimated.
-    Elastic-net and group penalties, drop sets and a log-likelihood score are not implemented."""
+    ``get_params`` returns what was given.
+
+    ``kappa='ml'`` estimates the dispersion by maximum likelihood (integer counts required):
+    ``fit`` alternates the fixed-kappa fit with ``nb2.profile`` (the likelihood's maximiser in
+    kappa at that fit's predictor) from the moment estimate (s^2 - ybar) / ybar^2 clipped to
+    [2^-6, 2^6], each round warm-started from the last, until |d ln kappa| <= 2^-20 (at most
+    ``ML_MAX_ROUNDS`` rounds).  ``kappa_`` is the float32 value the returned coefficients were
+    fitted at (``coef_`` is exactly the fixed-kappa fit at ``kappa_``), with ``kappa_n_rounds_``,
+    ``kappa_converged_``, ``kappa_at_bound_`` and ``n_iter_`` (the IRLS iterations of all
+    rounds); ``score`` and ``predict`` use ``kappa_``.  Counts without over-dispersion end at
+    the lower bound 2^-20 with a ``UserWarning`` (the Poisson limit).  ``objective()`` has no
+    value before the fit, so the CV grids refuse ``'ml'``: put kappa on the parameter grid with
+    ``score_method='ll'`` there.
+    Elastic-net and group penalties and drop sets are not implemented."""
+    ML_MAX_ROUNDS = 25
+    ML_TOL = 2.0 ** -20
     _params = ("kappa", "alpha", "fit_intercept", "solver", "max_iter", "tol", "warm_start",
                "verbose", "l1_ratio")
 
@@ -555,8 +575,30 @@ class NegativeBinomialRegressor(_EngineRegressor):
                          max_iter=max_iter, tol=tol, warm_start=warm_start, verbose=verbose,
                          l1_ratio=l1_ratio)
 
+    def _is_ml(self) -> bool:
+        return isinstance(self.kappa, str) and self.kappa == "ml"
+
+    def _kappa(self) -> float:
+        """The dispersion of predict / score: the given one, or the fitted ``kappa_``."""
+        if not self._is_ml():
+            return nb2_kappa(self.kappa)
+        if not hasattr(self, "kappa_"):
+            raise AttributeError("NegativeBinomialRegressor(kappa='ml') is not fitted yet: "
+                                 "kappa_ is set by fit")
+        return float(self.kappa_)
+
     def objective(self):
-        kappa = nb2_kappa(self.kappa)
+        if self._is_ml():
+            raise NotYetImplementedError(
+                "NegativeBinomialRegressor(kappa='ml') has no objective before it is fitted, and "
+                "a CV grid solves one (family, kappa) per launch: put kappa on the parameter "
+                "grid with score_method='ll' instead")
+        return self._objective_at(nb2_kappa(self.kappa))
+
+    def _objective(self):
+        return self._objective_at(self._kappa())
+
+    def _objective_at(self, kappa):
         if self.alpha < 0:
             raise ValueError("alpha must be >= 0")
         rho = float(self.l1_ratio)
@@ -569,12 +611,69 @@ class NegativeBinomialRegressor(_EngineRegressor):
         return Objective("irls", E.FAM_NB2_LOG, kappa, float(self.alpha), "n",
                          self.fit_intercept, int(self.max_iter))
 
+    def fit(self, X, y, sample_weight=None):
+        if not self._is_ml():
+            return super().fit(X, y, sample_weight)
+        import warnings
+        from . import nb2
+        if sample_weight is not None:
+            raise NotYetImplementedError("sample_weight is not used by the reference path")
+        obj = self._objective_at(1.0)                       # validates alpha / l1_ratio
+        Xh = X
+        X = _as2d(X)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if X.shape[0] != y.shape[0]:
+            raise ValueError(f"Found input variables with inconsistent numbers of samples: "
+                             f"[{X.shape[0]}, {y.shape[0]}]")
+        _check_y_range(1, y)
+        y = nb2.check_counts(y)
+        d = self._design(Xh)
+        n = X.shape[0]
+        prob = E.Problem(d, [y], [np.ones(n, np.uint8)])
+        tails = nb2.count_tails(prob)
+        c0, b0 = self._warm()
+        if c0 is not None and c0.shape[0] != X.shape[1]:
+            c0, b0 = None, None
+        kappa = nb2.moment_kappa(tails[0, 0], float(n))
+        n_iter, converged, at_bound = 0, False, False
+        for rnd in range(1, self.ML_MAX_ROUNDS + 1):
+            kfit = nb2_kappa(kappa)
+            req = E.FitReq(obj.family, kfit, obj.lam(n), 0, 0, obj.fit_intercept, obj.max_iter,
+                           c0, b0)
+            (res,), eta = E.irls(prob, [req])
+            n_iter += res.n_iter
+            ks, ab, _ = nb2.profile(prob, eta, [0], [0], [0], tails, start=[kfit])
+            kappa, at_bound = float(ks[0]), bool(ab[0])
+            if abs(math.log(kappa) - math.log(kfit)) <= self.ML_TOL:
+                converged = True
+                break
+            c0, b0 = res.coef, (res.intercept if obj.fit_intercept else None)
+        self._set_fitted(res.coef, res.intercept, n_iter)
+        self.kappa_ = kfit
+        self.kappa_n_rounds_ = rnd
+        self.kappa_converged_ = converged
+        self.kappa_at_bound_ = at_bound
+        if at_bound and kappa == nb2.KAPPA_LO:
+            warnings.warn("NegativeBinomialRegressor(kappa='ml'): the likelihood has no "
+                          "over-dispersion to fit (the Poisson limit); fitted at the lower bound "
+                          "kappa = 2^-20 -- PoissonRegressor is the model for these counts",
+                          UserWarning, stacklevel=2)
+        elif at_bound:
+            warnings.warn("NegativeBinomialRegressor(kappa='ml'): the likelihood still rises at "
+                          "the upper bound kappa = 2^10", UserWarning, stacklevel=2)
+        elif not converged:
+            warnings.warn(f"NegativeBinomialRegressor(kappa='ml'): kappa did not settle within "
+                          f"{self.ML_MAX_ROUNDS} rounds (last |d ln kappa| = "
+                          f"{abs(math.log(kappa) - math.log(kfit)):.3g})", UserWarning,
+                          stacklevel=2)
+        return self
+
     def score(self, X, y, sample_weight=None):
         """D^2, the fraction of NB2 deviance explained at the fit's kappa:
         1 - (sum loss + sum c) / (null + sum c), c the saturated constant."""
         y = np.asarray(y, dtype=np.float64).reshape(-1)
         _check_y_range(1, y)
-        kappa = nb2_kappa(self.kappa)
+        kappa = self._kappa()
         dev = float(np.sum(nb2_loss_np(kappa, y, self._linear_predictor(X))))
         const = float(np.sum(nb2_constant_np(kappa, y)))
         dev0 = nb2_null_np(kappa, float(y.size), float(y.sum()))

@@ -8,8 +8,10 @@ Restates the arithmetic of ``cv_glm_single_params`` / ``cv_glm_mult_params``
   (:180-181) — all of them in one batched IRLS over a single resident X (no
   ``X[idx_train, :]`` copies, :107-110);
 * train/test scores are the GLM ``score`` of the chosen ``score_method`` ('mse' ->
-  -mean((y - mu)^2), 'r2' -> R^2 or D^2), computed from device row sums
-  (sglm_score_sums) plus float64 mask statistics;
+  -mean((y - mu)^2), 'r2' -> R^2 or D^2, 'll' -> mean log-likelihood per scored row of the
+  Poisson / NB2 / Binomial families), computed from device row sums (sglm_score_sums) plus
+  float64 mask statistics ('ll': plus the y-only likelihood terms from one tail histogram per
+  (mask, response), nb2.count_tails -- no extra row pass per kappa);
 * ``cv_R2_score`` pools the test residuals of all splits against per-split test means
   (calc_R2 over concatenations, :196), ``cv_mse_score`` = mean squared pooled residual.
 
@@ -374,6 +376,11 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
     from .comm import RowComm, SimComm, row_slab
     dist = _dist() if shard and simulate is None else None
     irls_only = all(o.kind == "irls" for g in groups for o in g["objectives"])
+    from . import nb2
+    if score_method == "ll":                 # Normal / Gamma / Tweedie: refused before any work
+        for g in groups:
+            for o in g["objectives"]:
+                nb2.check_ll_family(o.family, o.power)
     if any(o.family == E.FAM_BINOMIAL_LOGIT for g in groups for o in g["objectives"]):
         from .estimators import check_binomial_y
         y = check_binomial_y(y)              # every row, before any device work
@@ -478,6 +485,37 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
     def objective(i):
         return groups[table[i][0]]["objectives"][table[i][1]]
 
+    # 'll': the y-only terms of the count likelihoods, from one histogram pass over the masks
+    # and responses (integer counts required); a (mask, response, family, kappa)'s constant is
+    # a host sum over its tail
+    tails, llc_cache = None, {}
+    if score_method == "ll" and any(nb2.needs_counts(o.family)
+                                    for g in groups for o in g["objectives"]):
+        err = None
+        try:
+            tails = nb2.count_tails(prob, comm)
+        except (ValueError, NotImplementedError) as e:
+            err = e
+        if dist is not None and comm is None:
+            # fit-sharded ranks hold different masks: the verdict is shared (one int
+            # all-reduce), so that every rank raises together, as for the y-range check
+            import torch
+            flag = torch.tensor([int(err is not None)], dtype=torch.int32,
+                                device="cuda" if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            if err is None and int(flag.item()):
+                err = ValueError("integer counts below 2^20 are required: refused on another "
+                                 "rank's rows")
+        if err is not None:
+            raise err
+
+    def llc(obj, r, m):
+        key = (obj.family, float(obj.power), r, m)
+        if key not in llc_cache:
+            llc_cache[key] = nb2.ll_const(None if tails is None else tails[m, r], obj.family,
+                                          obj.power)
+        return llc_cache[key]
+
     results = {}
     solve_groups = {}
     groupings, grouping_of = [], {}          # distinct 'gcd' groupings; objective id -> index
@@ -543,8 +581,11 @@ def run_multi(X, y, groups: Sequence[dict], score_method: str = "mse", coef0=Non
                                   _score("mse", obj, sums[q][1], sth))
             else:
                 st_te = ms.get(r, local[mt], pw)
-                sc["train"] = _score(score_method, obj, sums[q][0], ms.get(r, local[m], pw))
-                sc["test"] = _score(score_method, obj, sums[q][1], st_te)
+                ll = score_method == "ll"
+                sc["train"] = _score(score_method, obj, sums[q][0], ms.get(r, local[m], pw),
+                                     llc(obj, r, local[m]) if ll else None)
+                sc["test"] = _score(score_method, obj, sums[q][1], st_te,
+                                    llc(obj, r, local[mt]) if ll else None)
                 sc["ss_res"] = float(sums[q][1][0])
                 sc["sst"], sc["cnt_te"] = st_te["sst"], st_te["cnt"]
             results[i if dsets is None else (i, q % nds)] = (rr.coef, rr.intercept, rr.n_iter,
@@ -650,11 +691,13 @@ def _mask_count(idx, multiplicity, n, check=True):
     return float(np.unique(F.wrap_indices(idx, n)).size)
 
 
-def _score(method, obj: Objective, sums, st):
+def _score(method, obj: Objective, sums, st, llc=None):
     s2, sl = sums
     cnt = st["cnt"]
     if cnt == 0:
         return np.nan
+    if method == "ll":                       # mean log-likelihood: -(summed loss) + y-only terms
+        return (llc - sl) / cnt
     if method != "r2":
         return -s2 / cnt
     if obj.family == E.FAM_SQUARED:
