@@ -1097,6 +1097,61 @@ int sglm_group_cd_shared(const double* Q, int32_t p, const int32_t* qidx, int32_
                          int32_t max_sweeps, double tol, double* w, int32_t* sweeps,
                          sglm_stream_t stream);
 
+/* --- inference on fitted models: Fisher weights, float64 inverse, covariance blocks ---------
+ * (csrc/infer.hip; statsmodels GLM.fit().cov_params() / R vcov in the engine's sum scaling.)
+ * sglm_infer_rows: one row pass per launch row q < B, fit slot k = slots[q] (q when slots is
+ *   NULL), response r = fit_resp[k], mask m = fit_mask[k], read as sglm_link_weights reads them.
+ *   mode 0: w[i] = M[m][i] * v(eta[k][i]) with v the EXPECTED (Fisher) weight
+ *     SQUARED 1 | TWEEDIE_LOG mu^(2 - power) | BINOMIAL_LOGIT mu (1 - mu) | NB2_LOG mu / (1 + kappa mu)
+ *   (not the observed loss'' of sglm_link_weights: they differ for NB2, Gamma and Tweedie);
+ *   mode 1: w[i] = M[m][i] * s^2, s = dloss/deta (the score residual of sglm_link_update's R).
+ *   Binomial from e = exp(-|eta|), NB2 from exp(-|eta + ln kappa|) as the link code: finite for
+ *   every finite eta.  A weight below 2^-100 is written as 0 (its pieces would leave bf16's
+ *   normal range).  Wp: three f32 planes [3][B][ld], row q of each: the 24-bit significand of the
+ *   f32 w cut into three 8-bit pieces, most significant first -- every piece is >= 0 and exactly
+ *   a bf16 value, and (Wp0 + Wp1) + Wp2 is bitwise w; rows n <= i < ld are 0.
+ *   sums (optional, float64 [B][2] by launch row): { sum_i M (y - mu)^2 / V(mu), sum_i M } with
+ *   V = 1 | mu^power | mu (1 - mu) | mu + kappa mu^2, each term in float64 from the f32 eta and y;
+ *   fixed reduction order (a repeated call returns the same bits).
+ *   work: sglm_infer_rows_work_bytes(B, ld) when sums is given. */
+size_t sglm_infer_rows_work_bytes(int32_t B, int64_t ld);
+int sglm_infer_rows(int32_t family, float power, int32_t mode, int64_t n, int64_t ld, int32_t B,
+                    const int32_t* slots, const float* eta, const float* Y, const uint8_t* M,
+                    const int32_t* fit_resp, const int32_t* fit_mask, float* Wp, double* sums,
+                    void* work, sglm_stream_t stream);
+/* sglm_chol64_inverse: Ainv[f] = (U_f^T U_f)^-1 (float64 [nf][P][P], full and bitwise symmetric)
+ *   on the kept coordinates (state 0) of the factor sglm_chol64_factor left in U[f]; the rows and
+ *   columns of excluded, zero and dependent coordinates are exact 0.0.  No entry U[f][i][j] with
+ *   i > j is read.  Blocked on 64 x 64 tiles: the inverses of the diagonal tiles, the blocked
+ *   triangular inverse T = U^-1 one tile diagonal at a time, then Ainv = T T^T; plain float64
+ *   FMA in a fixed order.  P % 64 == 0, P <= 8192.  work: sglm_chol64_inverse_work_bytes(P, nf). */
+size_t sglm_chol64_inverse_work_bytes(int32_t P, int32_t nf);
+int sglm_chol64_inverse(const double* U, int32_t P, const uint8_t* state, int32_t nf,
+                        double* Ainv, void* work, sglm_stream_t stream);
+/* sglm_cov_groups: variances and per-group Wald statistics of nfit fits from Ainv = A^-1,
+ *   A = J + diag(lam on the p coefficients, 0 on the intercept at index p).  Fit f reads
+ *   Ainv[asrc[f]] and state[asrc[f]] (asrc NULL: f).  cov_type selects C:
+ *     0 'model'  C = scale[f] (Ainv - lam[f] Ainv D Ainv), D = identity on coordinates < p
+ *     1 'bayes'  C = scale[f] Ainv
+ *     2 'robust' C = Ainv M[f] Ainv, M float64 [nfit][P][P], symmetric, both triangles read
+ *                (the panel M Ainv[:, g] is formed 64 rows at a time); scale is not read.
+ *   M may be NULL unless cov_type == 2.  var[f][j] = C_jj, j < P (0 at coordinates that are not
+ *   kept).  The groups are a CSR in DEVICE memory over the p coefficients, with the conventions
+ *   and host validation of sglm_group_cd_shared (ng == 0: no groups).  For group g of fit f the
+ *   coordinates that are not kept leave the group; dof[f][g] = the k that remain,
+ *   stat[f][g] = beta_g^T (C_gg)^-1 beta_g (beta float64 [nfit][P]) by a Cholesky factor of the
+ *   k x k block in LDS, status[f][g] = 0, 1 (a non-positive pivot of C_gg: stat = NaN) or 2 (more
+ *   than sglm_cov_groups_kmax() = 64 columns in the group: stat = NaN).  cov (optional, float64
+ *   [nfit][P][P]) receives the whole of C, bitwise symmetric.  Sums run in a fixed order.
+ *   P % 64 == 0, p < P <= 8192. */
+int32_t sglm_cov_groups_kmax(void);
+int sglm_cov_groups(const double* Ainv, int32_t P, int32_t p, const int32_t* asrc,
+                    const uint8_t* state, const double* M, int32_t cov_type, int32_t nfit,
+                    const double* lam, const double* scale, const double* beta,
+                    const int32_t* goff, const int32_t* gcols, int32_t ng, double* var,
+                    double* stat, int32_t* dof, int32_t* status, double* cov,
+                    sglm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,8 +277,9 @@ __global__ void __launch_bounds__(kGT) group_cd_kernel(
 }
 
 // The group CSR on the host (it is validated there; at most 2 x 4097 ints): offsets start at 0,
-// end at p and increase strictly; the column list is a permutation of 0..p-1.
-static int read_groups(const char* who, int32_t p, const int32_t* goff, const int32_t* gcols,
+// end at p and increase strictly; the column list is a permutation of 0..p-1.  (Shared with
+// sglm_cov_groups, infer.hip.)
+int read_groups(const char* who, int32_t p, const int32_t* goff, const int32_t* gcols,
                        int32_t ng, hipStream_t s, int32_t* kmax) {
     std::vector<int32_t> off((size_t)ng + 1), cols((size_t)p);
     if (hipMemcpyAsync(off.data(), goff, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s) !=

@@ -203,6 +203,14 @@ class GLM():
         resids.append(residuals)
         mean_resids.append(mean_residuals)
 
+    def inference(self, X, y, **kw):
+        """Standard errors, z-tests, scale and (with ``groups=``) per-group Wald tests of the
+        fitted model on the design it was fitted on (``sglm_hip.inference.infer``; keywords
+        ``groups``, ``cov_type``, ``scale``, ``return_cov``)."""
+        if type(X) == pd.DataFrame:
+            X = host_matrix(X)
+        return self.model.inference(X, y, **kw)
+
     def get_residuals(self, X: Union[np.ndarray, pd.DataFrame],
                       y: Union[np.ndarray, pd.Series]) -> Tuple[np.ndarray, np.ndarray]:
         residuals = (y - self.predict(X))

@@ -180,20 +180,54 @@ def event_groups(X):
     frame's own column-to-source map while it is lazy, else by ``add_timeshifts_to_col_list``'s
     naming (``f"{name}_{shift}"`` belongs to ``name`` when the frame has a column ``name``).  A
     column that is no shift of another column is a group of its own."""
+    ids = {}
+    return np.asarray([ids.setdefault(b, len(ids)) for b in _event_bases(X)], dtype=np.int64)
+
+
+def _event_bases(X):
+    """The base column name of every column of ``X`` (``event_groups``'s rule)."""
     import re
     cols = list(X.columns)
     spec = X._spec if isinstance(X, LagFrame) and X.is_lazy else None
     names = set(str(c) for c in cols)
     pat = re.compile(r"(.+)_(-?\d+)$")
-    ids, out = {}, []
+    out = []
     for c in cols:
         if spec is not None:
             base = c if c in X._overlay else spec[c][0]
         else:
             m = pat.match(str(c))
             base = m.group(1) if m and m.group(1) in names else str(c)
-        out.append(ids.setdefault(base, len(ids)))
-    return np.asarray(out, dtype=np.int64)
+        out.append(base)
+    return out
+
+
+def event_wald(X, y, glm, **kw):
+    """Wald test of every event kernel of a fitted ``glm`` (an ``'irls'`` model: OLS / Ridge,
+    Poisson, Gamma, Tweedie, Binomial, NB2) on the lagged frame ``X`` it was fitted on: a
+    DataFrame indexed by event name (``event_groups``'s groups) with ``dof`` (the kernel's
+    columns), ``wald`` = w_g^T C_gg^-1 w_g and its chi-square ``pvalue``.  One fit and one
+    covariance, where the leave-one-event-out grid refits per event.  ``kw``: ``cov_type``,
+    ``scale`` (``sglm_hip.inference.infer``)."""
+    from sglm_hip import inference
+    bases = _event_bases(X)
+    r = inference.infer(X, y, glm, groups=event_groups(X), **kw)
+    return pd.DataFrame({"dof": r.group_dof, "wald": r.group_stat, "pvalue": r.group_pvalue},
+                        index=pd.Index(list(dict.fromkeys(bases)), name="event"))
+
+
+def kernel_bands(X, y, glm, level=0.95, **kw):
+    """Pointwise confidence bands of every coefficient of a fitted ``glm`` on the frame ``X`` it
+    was fitted on: a DataFrame per column with ``coef``, ``se`` and the normal-theory band
+    ``lo`` / ``hi`` = coef -+ z_level se (pointwise, not simultaneous).  ``kw`` as ``event_wald``."""
+    import scipy.special
+    from sglm_hip import inference
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level must lie in (0, 1). Got {level!r} instead.")
+    r = inference.infer(X, y, glm, **kw)
+    zq = float(np.sqrt(2.0) * scipy.special.erfinv(level))
+    return pd.DataFrame({"coef": r.coef, "se": r.se, "lo": r.coef - zq * r.se,
+                         "hi": r.coef + zq * r.se}, index=pd.Index(list(X.columns), name="column"))
 
 
 def reduce_cv_result(r, drop, glm_kwargs, model_name):

@@ -203,6 +203,14 @@ SIGNATURES = {
     "sglm_group_bound": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "sglm_group_cd_shared": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                        _i32, C.c_double, _vp, _vp, _vp]),
+    "sglm_infer_rows_work_bytes": (_sz, [_i32, _i64]),
+    "sglm_infer_rows": (C.c_int, [_i32, _f32, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp]),
+    "sglm_chol64_inverse_work_bytes": (_sz, [_i32, _i32]),
+    "sglm_chol64_inverse": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "sglm_cov_groups_kmax": (_i32, []),
+    "sglm_cov_groups": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                  _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -299,6 +299,12 @@ class _EngineRegressor:
             return sigmoid_np(eta)
         return np.exp(eta) if obj.family in (E.FAM_TWEEDIE_LOG, E.FAM_NB2_LOG) else eta
 
+    def inference(self, X, y, **kw):
+        """Standard errors, z-tests, scale and (with ``groups=``) per-group Wald tests of this
+        fitted model on the design ``X`` it was fitted on: ``inference.infer(X, y, self, **kw)``."""
+        from . import inference
+        return inference.infer(X, y, self, **kw)
+
     def score(self, X, y, sample_weight=None):
         """R^2 (Gaussian estimators, sklearn RegressorMixin.score)."""
         y = np.asarray(y, dtype=np.float64).reshape(-1)

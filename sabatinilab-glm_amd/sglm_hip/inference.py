@@ -1,0 +1,343 @@
+"""Standard errors, covariance matrices and per-group Wald tests of fitted models, batched over
+many models on one resident design (csrc/infer.hip).
+
+For a converged fit (w, b) of an ``'irls'`` objective with penalty lam on w (the engine's sum
+scaling, ``FitReq.lam``), J = X~^T diag(m v(eta)) X~ is the expected information (X~ the design
+with its ones column, v the Fisher weight of the family) and A = J + diag(lam on w, 0 on b):
+
+  cov_type='model'   C = phi A^-1 J A^-1 = phi (A^-1 - lam A^-1 D A^-1)   (default; at lam = 0
+                     phi J^-1: statsmodels ``cov_params()``, R ``vcov``)
+  cov_type='bayes'   C = phi A^-1
+  cov_type='robust'  C = A^-1 M A^-1, M = X~^T diag(m s^2) X~, s = dloss/deta   (HC0)
+
+phi = 1 for Poisson, Binomial and NB2 and the Pearson estimate sum m (y - mu)^2 / V(mu) / (n - df)
+for Normal, Gamma and Tweedie, df = tr(A^-1 J); ``scale='pearson'`` forces the estimate on any
+family (quasi-Poisson), a float fixes phi.  A ``NegativeBinomialRegressor(kappa='ml')`` model is
+taken at its fitted ``kappa_`` as if that were known: the errors do not carry the uncertainty of
+the dispersion.
+
+Not covered (refused where it can be told): cluster-robust covariance, mixed or non-binary
+designs, models fitted with an L1 or group penalty (naive errors after selection are wrong),
+likelihood-ratio tests, t and F reference distributions.
+"""
+from __future__ import annotations
+
+import os
+import warnings
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import engine as E
+from .estimators import NotYetImplementedError
+
+COV_TYPES = {"model": 0, "bayes": 1, "robust": 2}
+MAX_P = 4096
+# device bytes the float64 P x P buffers of one chunk of fits may take (factor, inverse and its
+# work, Grams, the optional covariance)
+INFER_BYTES = float(os.environ.get("SGLM_INFER_BYTES", "8e9"))
+# families whose dispersion is 1 unless scale= says otherwise
+_UNIT_SCALE = (E.FAM_BINOMIAL_LOGIT, E.FAM_NB2_LOG)
+
+
+@dataclass
+class Inference:
+    """Inference of one fitted model (see the module docstring).  ``se`` / ``z`` / ``pvalues``
+    are per coefficient (NaN at a coefficient of an all-zero column); the ``group_*`` arrays are
+    per group of ``groups`` in the order of ``group_ids`` (None without groups); ``cov`` is the
+    (p + 1) x (p + 1) matrix with the intercept last, when asked for."""
+    coef: np.ndarray
+    intercept: float
+    se: np.ndarray
+    intercept_se: float
+    z: np.ndarray
+    pvalues: np.ndarray
+    scale: float
+    df: float
+    n: float
+    group_ids: Optional[np.ndarray] = None
+    group_dof: Optional[np.ndarray] = None
+    group_stat: Optional[np.ndarray] = None
+    group_pvalue: Optional[np.ndarray] = None
+    cov: Optional[np.ndarray] = None
+
+
+def check_models(models, cov_type="model", scale=None):
+    """The objectives of fitted models that inference covers, refusing the rest (no device)."""
+    if cov_type not in COV_TYPES:
+        raise ValueError(f"cov_type must be one of {sorted(COV_TYPES)}. Got {cov_type!r} instead.")
+    if scale is not None and scale != "pearson":
+        if isinstance(scale, str) or not (np.isfinite(float(scale)) and float(scale) > 0):
+            raise ValueError(f"scale must be None, 'pearson' or a float > 0. Got {scale!r} instead.")
+    objs = []
+    for m in models:
+        if not hasattr(m, "_objective") and hasattr(m, "model"):
+            m = m.model                            # a sglm.GLM wrapper
+        if not hasattr(m, "coef_"):
+            raise AttributeError(f"This {type(m).__name__} instance is not fitted yet: call fit "
+                                 "before inference")
+        obj = m._objective()
+        if obj.kind != "irls":
+            what = {"cd": "an L1 / elastic-net penalty (Lasso, ElasticNet)",
+                    "gcd": "a group-lasso penalty (GroupLasso)",
+                    "pn": "an L1 / elastic-net penalty on a log link"}.get(obj.kind, obj.kind)
+            raise NotYetImplementedError(
+                f"inference on a model fitted with {what} (objective kind {obj.kind!r}): naive "
+                "standard errors after selection are wrong")
+        if m.coef_.shape[0] > MAX_P - 1:
+            raise NotYetImplementedError(f"inference with p = {m.coef_.shape[0]} > {MAX_P - 1} "
+                                         "columns")
+        objs.append((m, obj))
+    return objs
+
+
+def check_design(d):
+    """Refuse the designs inference does not cover (mixed, non-binary, row-sharded, p > 4096)."""
+    if d.slab is not None:
+        raise NotYetImplementedError("inference on a row-sharded problem")
+    if d.cont is not None:
+        raise NotYetImplementedError("inference on a mixed 0/1 + continuous design")
+    if d.xbits is None:
+        raise NotYetImplementedError("inference on a non-binary design")
+    if d.P > MAX_P:
+        raise NotYetImplementedError(f"inference with p = {d.p} > {MAX_P - 1} columns")
+
+
+def group_lists(groups, p):
+    """(ids, goff, gcols, sizes) of one integer id per column (glasso.group_csr's CSR)."""
+    from . import glasso
+    ids = np.asarray(groups).reshape(-1)
+    goff, gcols = glasso.group_csr(ids, p)
+    return np.unique(ids), goff, gcols, np.diff(goff)
+
+
+class _Grams:
+    """The caller-owned buffers E._syrk forms Grams from outside a solve: weights W [B][ld] and
+    Grams H [B][P][P] by slot, the slots' masks and the problem (no ``wlink``: W is ours)."""
+
+    def __init__(self, prob, fit_mask, B, dev):
+        d = prob.design
+        self.prob, self.fit_mask, self.up = prob, np.asarray(fit_mask, dtype=np.int32), None
+        self.W = None
+        self.H = torch.empty((B, d.P, d.P), dtype=torch.float32, device=dev)
+
+    def gram64(self, W, masks, exact, st):
+        """triu(X~^T diag(W[k]) X~) of every row k of W (mask masks[k]) in float64 (bf16 MFMA,
+        f32 accumulate; W is bf16-exact, so the products are exact)."""
+        d = self.prob.design
+        self.W, self.fit_mask = W, np.asarray(masks, dtype=np.int32)
+        B = W.shape[0]
+        E._syrk(d, self, np.arange(B, dtype=np.int32), (d.n + 31) // 32,
+                (d.P // 256) * (d.P // 256 + 1) // 2, None, st, exact=exact)
+        return torch.triu(self.H[:B]).double()
+
+
+def _row_pass(prob, fam, power, mode, sel, eta, fit_resp_d, fit_mask_d, want_sums, st):
+    """sglm_infer_rows over the fits ``sel`` (slots of eta): planes [3][len(sel)][ld], sums."""
+    d = prob.design
+    dev = d.device
+    nb = len(sel)
+    Wp = torch.empty((3, nb, d.ld), dtype=torch.float32, device=dev)
+    sums = torch.zeros((nb, 2), dtype=torch.float64, device=dev) if want_sums else None
+    work = E._work(E._lib.query("sglm_infer_rows_work_bytes", nb, d.ld), dev, "infer") \
+        if want_sums else None
+    slots = torch.from_numpy(np.asarray(sel, dtype=np.int32)).to(dev)
+    E._lib.call("sglm_infer_rows", int(fam), float(power), int(mode), d.n, d.ld, nb, E._p(slots),
+                E._p(eta), E._p(prob.Y), E._p(prob.M), E._p(fit_resp_d), E._p(fit_mask_d),
+                E._p(Wp), E._p(sums), E._p(work), st)
+    return Wp, sums
+
+
+def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, masks,
+                  goff=None, gcols=None, cov_type="model", scale=None, return_cov=False):
+    """Inference of B fits on one problem: per fit its family, power (kappa for NB2), penalty
+    ``lam`` (sum scaling), whether it has an intercept, its coefficients, response and mask.
+    Returns a dict of host arrays: var (B, P), state (B, P), scale, df, n (B), stat / dof /
+    status (B, ng) with groups, cov (B, P, P) when asked for."""
+    d = prob.design
+    check_design(d)
+    P, p, ld, dev = d.P, d.p, d.ld, d.device
+    B = len(fams)
+    ct = COV_TYPES[cov_type]
+    st = E._stream()
+    ng = 0 if goff is None else len(goff) - 1
+    goff_d = gcols_d = None
+    if ng:
+        goff_d = torch.from_numpy(np.asarray(goff, dtype=np.int32)).to(dev)
+        gcols_d = torch.from_numpy(np.asarray(gcols, dtype=np.int32)).to(dev)
+    out = {k: [] for k in ("var", "state", "scale", "df", "n", "stat", "dof", "status", "cov")}
+    # P x P float64 buffers alive per fit: U, T, Ainv, the Gram sum (+ M, + cov), f32 H twice
+    per = 8 * P * P * (4 + (ct == 2) + bool(return_cov)) + 8 * P * P
+    chunk = max(1, int(INFER_BYTES // per))
+    for c0 in range(0, B, chunk):
+        sel = np.arange(c0, min(B, c0 + chunk))
+        nb = len(sel)
+        beta = np.zeros((nb, P))
+        for i, k in enumerate(sel):
+            beta[i, :p] = coefs[k]
+            beta[i, p] = intercepts[k] if icpts[k] else 0.0
+        beta_d = torch.from_numpy(beta).to(dev)
+        eta = d.eta(beta_d.float())
+        fr = torch.tensor([int(resps[k]) for k in sel], dtype=torch.int32, device=dev)
+        fm_h = np.array([int(masks[k]) for k in sel], dtype=np.int32)
+        fm = torch.from_numpy(fm_h).to(dev)
+        gr = _Grams(prob, fm_h, nb, dev)
+        J32 = torch.zeros((nb, P, P), dtype=torch.float32, device=dev)
+        M64 = torch.zeros((nb, P, P), dtype=torch.float64, device=dev) if ct == 2 else None
+        sums = torch.zeros((nb, 2), dtype=torch.float64, device=dev)
+        exact = np.zeros(nb, dtype=bool)
+        for fam, power in sorted(set((int(fams[k]), float(powers[k])) for k in sel)):
+            loc = np.array([i for i, k in enumerate(sel)
+                            if (int(fams[k]), float(powers[k])) == (fam, power)])
+            loc_d = torch.from_numpy(loc).to(dev)
+            if fam == E.FAM_SQUARED:
+                # the exact integer Gram at the mask multiplicities (as engine._gram_ls)
+                W = prob.M[fm[loc_d].long()].float()
+                J32[loc_d] = gr.gram64(W, fm_h[loc], True, st).float()
+                exact[loc] = True
+                _, s = _row_pass(prob, fam, power, 0, loc, eta, fr, fm, True, st)
+            else:
+                Wp, s = _row_pass(prob, fam, power, 0, loc, eta, fr, fm, True, st)
+                J = gr.gram64(Wp[0], fm_h[loc], False, st)
+                J += gr.gram64(Wp[1], fm_h[loc], False, st)
+                J += gr.gram64(Wp[2], fm_h[loc], False, st)
+                J32[loc_d] = J.float()          # the f32 triangle sglm_chol64_factor reads
+            sums[loc_d] = s
+            if ct == 2:
+                Wp, _ = _row_pass(prob, fam, power, 1, loc, eta, fr, fm, False, st)
+                Mm = gr.gram64(Wp[0], fm_h[loc], False, st)
+                Mm += gr.gram64(Wp[1], fm_h[loc], False, st)
+                Mm += gr.gram64(Wp[2], fm_h[loc], False, st)
+                M64[loc_d] = Mm + torch.triu(Mm, 1).transpose(1, 2)
+        # A = J + diag(lam on w, 0 on b): float64 factor, then the inverse
+        lam = np.array([float(lams[k]) for k in sel])
+        fi = np.array([1.0 if icpts[k] else 0.0 for k in sel])
+        lam_d = torch.from_numpy(lam).to(dev)
+        dshift = torch.full((nb, P), -1.0, dtype=torch.float32, device=dev)
+        dshift[:, :p] = lam_d[:, None].float()
+        dshift[:, p] = torch.from_numpy(fi - 1.0).to(dev).float()
+        lamp = torch.zeros((nb, P), dtype=torch.float64, device=dev)
+        lamp[:, :p] = lam_d[:, None]
+        U = torch.empty((nb, P, P), dtype=torch.float64, device=dev)
+        state = torch.empty((nb, P), dtype=torch.uint8, device=dev)
+        nulls = torch.empty((nb, P), dtype=torch.int32, device=dev)
+        counts = torch.zeros((nb, 2), dtype=torch.int32, device=dev)
+        ident = torch.arange(nb, dtype=torch.int32, device=dev)
+        work = E._work(E._lib.query("sglm_chol64_work_bytes", P, nb), dev, "chol64")
+        # an exact (integer) Gram takes the exact rank threshold, an f32-accumulated one the f32
+        # threshold, as engine._Factor64; a chunk mixing both takes the f32 one
+        small = max(prob.mask_count(int(v)) for v in fm_h) < 2 ** 24
+        tol = E.RANK_TOL_EXACT if exact.all() and small else E.RANK_TOL_F32
+        E._lib.call("sglm_chol64_factor", E._p(J32), P, E._p(ident), E._p(dshift), E._p(lamp),
+                    E._p(ident), nb, tol, E._p(U), E._p(state), E._p(nulls), E._p(counts),
+                    E._p(work), st)
+        cnt = counts.cpu().numpy()
+        if cnt[:, 0].any():
+            bad = int(np.argmax(cnt[:, 0] > 0))
+            raise ValueError(f"the model is not identified: {int(cnt[bad, 0])} coordinate(s) of "
+                             f"fit {int(sel[bad])} are linearly dependent on the others (add a "
+                             "penalty or drop the columns)")
+        Ainv = torch.empty((nb, P, P), dtype=torch.float64, device=dev)
+        T = torch.empty(E._lib.query("sglm_chol64_inverse_work_bytes", P, nb), dtype=torch.uint8,
+                        device=dev)
+        E._lib.call("sglm_chol64_inverse", E._p(U), P, E._p(state), nb, E._p(Ainv), E._p(T), st)
+        del U, T
+        # df = tr(A^-1 J) = kept coordinates - lam sum_{j < p} (A^-1)_jj; the Pearson scale
+        kept = (state == 0).sum(dim=1).double()
+        df = kept - lam_d * torch.diagonal(Ainv, dim1=1, dim2=2)[:, :p].sum(dim=1)
+        nrow = sums[:, 1]
+        pearson = sums[:, 0] / (nrow - df)
+        if scale == "pearson":
+            phi = pearson
+        elif scale is not None:
+            phi = torch.full_like(pearson, float(scale))
+        else:
+            unit = np.array([int(fams[k]) in _UNIT_SCALE
+                             or (int(fams[k]) == E.FAM_TWEEDIE_LOG and float(powers[k]) == 1.0)
+                             for k in sel])
+            phi = torch.where(torch.from_numpy(unit).to(dev), torch.ones_like(pearson), pearson)
+        phi = phi.contiguous()
+        var = torch.zeros((nb, P), dtype=torch.float64, device=dev)
+        stat = torch.zeros((nb, max(ng, 1)), dtype=torch.float64, device=dev)
+        dof = torch.zeros((nb, max(ng, 1)), dtype=torch.int32, device=dev)
+        status = torch.zeros((nb, max(ng, 1)), dtype=torch.int32, device=dev)
+        cov = torch.zeros((nb, P, P), dtype=torch.float64, device=dev) if return_cov else None
+        E._lib.call("sglm_cov_groups", E._p(Ainv), P, p, None, E._p(state), E._p(M64), ct, nb,
+                    E._p(lam_d), E._p(phi), E._p(beta_d), E._p(goff_d), E._p(gcols_d), ng,
+                    E._p(var), E._p(stat), E._p(dof), E._p(status), E._p(cov), st)
+        for key, t in (("var", var), ("state", state), ("scale", phi), ("df", df), ("n", nrow),
+                       ("stat", stat), ("dof", dof), ("status", status)):
+            out[key].append(t.cpu().numpy())
+        if return_cov:
+            out["cov"].append(cov.cpu().numpy())
+    res = {k: np.concatenate(v) for k, v in out.items() if v}
+    if not ng:
+        for k in ("stat", "dof", "status"):
+            res.pop(k)
+    return res
+
+
+def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=False):
+    """Inference of one fitted estimator or a list of them (e.g. one per alpha or per
+    response) on the design ``X`` they were fitted on: a list of ``Inference`` (one, not a list,
+    for a single model).  ``y``: one response vector, or one per model.  ``groups``: one integer
+    id per column (``sglm_ez.event_groups``) for per-group Wald tests."""
+    import scipy.special
+    single = not isinstance(models, (list, tuple))
+    models = [models] if single else list(models)
+    pairs = check_models(models, cov_type, scale)
+    B = len(pairs)
+    if isinstance(y, (list, tuple)) and len(y) == B and np.ndim(y[0]) >= 1:
+        ys = [np.asarray(v, dtype=np.float64).reshape(-1) for v in y]
+    else:
+        ys = [np.asarray(y, dtype=np.float64).reshape(-1)]
+    resps = list(range(B)) if len(ys) == B and B > 1 else [0] * B
+    p = pairs[0][0].coef_.shape[0]
+    for m, _ in pairs:
+        if m.coef_.shape[0] != p:
+            raise ValueError("the models have different numbers of coefficients")
+    ids = goff = gcols = None
+    if groups is not None:
+        ids, goff, gcols, sizes = group_lists(groups, p)
+    d = pairs[0][0]._design(X)
+    if d.p != p:
+        raise ValueError(f"X has {d.p} features, but the models are expecting {p} features")
+    check_design(d)
+    if groups is not None:
+        kmax = E._lib.query("sglm_cov_groups_kmax")
+        if np.any(sizes > kmax):
+            warnings.warn(f"{int(np.sum(sizes > kmax))} group(s) have more than {kmax} columns: "
+                          "their Wald statistics are NaN", UserWarning, stacklevel=2)
+    prob = E.Problem(d, ys, [np.ones(d.n, np.uint8)])
+    r = infer_problem(prob, [o.family for _, o in pairs], [o.power for _, o in pairs],
+                      [o.lam(float(d.n)) for _, o in pairs],
+                      [o.fit_intercept for _, o in pairs], [m.coef_ for m, _ in pairs],
+                      [m.intercept_ for m, _ in pairs], resps, [0] * B, goff, gcols, cov_type,
+                      scale, return_cov)
+    res = []
+    for k, (m, o) in enumerate(pairs):
+        var = r["var"][k].copy()
+        var[r["state"][k] != 0] = np.nan
+        with np.errstate(invalid="ignore", divide="ignore"):
+            se_all = np.sqrt(var)
+            coef = np.asarray(m.coef_, dtype=np.float64)
+            z = coef / se_all[:p]
+            pv = scipy.special.erfc(np.abs(z) / np.sqrt(2.0))
+        inf = Inference(coef=coef.copy(), intercept=float(m.intercept_), se=se_all[:p],
+                        intercept_se=float(se_all[p]) if o.fit_intercept else float("nan"),
+                        z=z, pvalues=pv, scale=float(r["scale"][k]), df=float(r["df"][k]),
+                        n=float(r["n"][k]))
+        if groups is not None:
+            stat, dof = r["stat"][k], r["dof"][k].astype(np.int64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                gp = np.where(dof > 0, scipy.special.gammaincc(np.maximum(dof, 1) / 2.0,
+                                                               stat / 2.0), np.nan)
+            inf.group_ids, inf.group_dof, inf.group_stat, inf.group_pvalue = ids, dof, stat, gp
+        if return_cov:
+            keep = np.r_[np.arange(p), p]
+            inf.cov = r["cov"][k][np.ix_(keep, keep)]
+        res.append(inf)
+    return res[0] if single else res
+
