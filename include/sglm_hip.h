@@ -543,7 +543,6 @@ int sglm_chol64_drop_solve_add(const double* U, int32_t P, const uint8_t* state,
 int sglm_step_scalars(int32_t P, int32_t ncoef, int32_t B, const int32_t* slots, const double* g,
                       const double* beta, const float* delta, const double* lamp,
                       const double* t, int32_t T, double* out, sglm_stream_t stream);
-/* beta[k] += step[q] * delta[k] for k = slots[q], q < B (float64 coefficients). */
 /* sglm_step_decide: the Newton iteration's decisions for na active fits (slots act) on the
  * device -- engine.irls' stage-1 Armijo search over ts[1..4] from the trial losses L [na][5]
  * and the step scalars sc [na][6 + nts] (sglm_loss_trials_max / sglm_step_scalars), the stopping
@@ -569,6 +568,7 @@ int sglm_step_decide(int32_t na, const int32_t* act, const double* L, const doub
 int sglm_aa_step(int32_t P, int32_t p, int32_t na, const int32_t* slots, const uint8_t* sel,
                  const float* tprev, float* delta, float* raw_prev, const float* used_prev,
                  const double* gtot, float* rm, sglm_stream_t stream);
+/* beta[k] += step[q] * delta[k] for k = slots[q], q < B (float64 coefficients). */
 int sglm_step_update(int32_t P, int32_t B, const int32_t* slots, const double* step,
                      const float* delta, double* beta, sglm_stream_t stream);
 
