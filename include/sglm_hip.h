@@ -1152,6 +1152,45 @@ int sglm_cov_groups(const double* Ainv, int32_t P, int32_t p, const int32_t* asr
                     double* stat, int32_t* dof, int32_t* status, double* cov,
                     sglm_stream_t stream);
 
+/* --- cluster-robust covariance: the meat M = sum_c g_c g_c^T of A^-1 M A^-1 ------------------
+ * (csrc/cluster.hip; statsmodels cov_type='cluster' / R sandwich::vcovCL.  g_c = sum over the
+ * rows i of cluster c of m_i s_i x~_i; sglm_cov_groups reads M as its cov_type 2 meat.)
+ * sglm_infer_scores: the arguments of sglm_infer_rows up to fit_mask, read the same way.
+ *   s[q][i] = M[m][i] * dloss/deta (float64 [B][ld] by launch row q), the SIGNED score residual
+ *     SQUARED eta - y | TWEEDIE_LOG mu^(2 - power) - y mu^(1 - power) | BINOMIAL_LOGIT mu - y |
+ *     NB2_LOG (mu - y) / (1 + kappa mu)
+ *   evaluated in float64 from the f32 eta and y, Binomial from exp(-|eta|) and NB2 from the side of
+ *   eta + ln kappa as sglm_infer_rows: finite for every finite eta.  Rows n <= i < ld are 0.
+ * sglm_cluster_scores: the rows are cut into R runs, run r = rows roff[r] .. roff[r + 1] - 1
+ *   (DEVICE int32 [R + 1], read back and validated on the host: 0 <= roff[0], strictly ascending,
+ *   roff[R] <= n); a run is a maximal stretch of rows of one cluster.
+ *   S[q][r][j] = sum_{roff[r] <= i < roff[r+1]} bit_j(i) s[q][i]   (float64 [B][R][P]), bit_j the
+ *   column plane j of xbits [P][ld/32] (sglm_pack_bits / sglm_lag_bits; the ones column through
+ *   its plane), s float64 [B][ld].  The rows of a run are added in ascending order under the
+ *   bit's mask (the products are exact, only the sums round): the order depends on neither the
+ *   launch nor the fits that share it, a run may be shorter than a word, span any number of tiles
+ *   and end anywhere in a word.  One pass over the planes for every 4 fits.
+ *   P % 256 == 0, P <= 8192, ld % 32 == 0, n <= ld < 2^31, n <= 65535 * 1024.
+ * sglm_cluster_meat: Mout[q] = sum_c g_c g_c^T (float64 [B][P][P], both triangles, bitwise
+ *   symmetric: the upper 64 x 64 tiles are computed and mirrored), g_c = the sum of the runs
+ *   cruns[coff[c] .. coff[c + 1]) of cluster c < G in that order (a CSR in DEVICE memory, read back
+ *   and validated on the host: every run once, ascending inside a cluster; work receives the g_c).
+ *   coff == NULL: every cluster is one run (R == G), S is read as the g_c and work is not used.
+ *   The rank-G update runs on v_mfma_f64_16x16x4_f64 over the clusters in ascending order, four
+ *   per instruction: a repeated call returns the same bits.
+ *   work: sglm_cluster_meat_work_bytes(P, B, G) when coff is given.  P % 256 == 0, P <= 8192. */
+int sglm_infer_scores(int32_t family, float power, int64_t n, int64_t ld, int32_t B,
+                      const int32_t* slots, const float* eta, const float* Y, const uint8_t* M,
+                      const int32_t* fit_resp, const int32_t* fit_mask, double* s,
+                      sglm_stream_t stream);
+int sglm_cluster_scores(const uint32_t* xbits, int64_t ld, int32_t P, int64_t n, const double* s,
+                        int32_t B, const int32_t* roff, int32_t R, double* S,
+                        sglm_stream_t stream);
+size_t sglm_cluster_meat_work_bytes(int32_t P, int32_t B, int32_t G);
+int sglm_cluster_meat(const double* S, int32_t P, int32_t B, int32_t R, const int32_t* coff,
+                      const int32_t* cruns, int32_t G, double* Mout, void* work,
+                      sglm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

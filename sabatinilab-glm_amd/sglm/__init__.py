@@ -206,7 +206,8 @@ class GLM():
     def inference(self, X, y, **kw):
         """Standard errors, z-tests, scale and (with ``groups=``) per-group Wald tests of the
         fitted model on the design it was fitted on (``sglm_hip.inference.infer``; keywords
-        ``groups``, ``cov_type``, ``scale``, ``return_cov``)."""
+        ``groups``, ``cov_type``, ``scale``, ``return_cov`` and, for ``cov_type='cluster'``,
+        ``clusters`` -- one trial or session label per row -- and ``cluster_correction``)."""
         if type(X) == pd.DataFrame:
             X = host_matrix(X)
         return self.model.inference(X, y, **kw)

@@ -208,7 +208,9 @@ def event_wald(X, y, glm, **kw):
     DataFrame indexed by event name (``event_groups``'s groups) with ``dof`` (the kernel's
     columns), ``wald`` = w_g^T C_gg^-1 w_g and its chi-square ``pvalue``.  One fit and one
     covariance, where the leave-one-event-out grid refits per event.  ``kw``: ``cov_type``,
-    ``scale`` (``sglm_hip.inference.infer``)."""
+    ``scale`` and, for ``cov_type='cluster'``, ``clusters`` (one trial or session label per row
+    of ``X``) and ``cluster_correction`` (``sglm_hip.inference.infer``).  With G clusters a
+    kernel of more than G - 1 columns has no clustered statistic: NaN, with a warning."""
     from sglm_hip import inference
     bases = _event_bases(X)
     r = inference.infer(X, y, glm, groups=event_groups(X), **kw)
@@ -219,7 +221,8 @@ def event_wald(X, y, glm, **kw):
 def kernel_bands(X, y, glm, level=0.95, **kw):
     """Pointwise confidence bands of every coefficient of a fitted ``glm`` on the frame ``X`` it
     was fitted on: a DataFrame per column with ``coef``, ``se`` and the normal-theory band
-    ``lo`` / ``hi`` = coef -+ z_level se (pointwise, not simultaneous).  ``kw`` as ``event_wald``."""
+    ``lo`` / ``hi`` = coef -+ z_level se (pointwise, not simultaneous).  ``kw`` as ``event_wald``
+    (``cov_type='cluster', clusters=trial_ids`` for bands robust to within-trial correlation)."""
     import scipy.special
     from sglm_hip import inference
     if not 0.0 < level < 1.0:

@@ -211,6 +211,11 @@ SIGNATURES = {
     "sglm_cov_groups_kmax": (_i32, []),
     "sglm_cov_groups": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                   _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sglm_infer_scores": (C.c_int, [_i32, _f32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
+    "sglm_cluster_scores": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "sglm_cluster_meat_work_bytes": (_sz, [_i32, _i32, _i32]),
+    "sglm_cluster_meat": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
 }
 
 

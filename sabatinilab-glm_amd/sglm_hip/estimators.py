@@ -301,7 +301,8 @@ class _EngineRegressor:
 
     def inference(self, X, y, **kw):
         """Standard errors, z-tests, scale and (with ``groups=``) per-group Wald tests of this
-        fitted model on the design ``X`` it was fitted on: ``inference.infer(X, y, self, **kw)``."""
+        fitted model on the design ``X`` it was fitted on: ``inference.infer(X, y, self, **kw)``
+        (``cov_type='cluster', clusters=ids`` for the covariance clustered by trial or session)."""
         from . import inference
         return inference.infer(X, y, self, **kw)
 

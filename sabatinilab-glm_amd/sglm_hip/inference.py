@@ -9,6 +9,14 @@ with its ones column, v the Fisher weight of the family) and A = J + diag(lam on
                      phi J^-1: statsmodels ``cov_params()``, R ``vcov``)
   cov_type='bayes'   C = phi A^-1
   cov_type='robust'  C = A^-1 M A^-1, M = X~^T diag(m s^2) X~, s = dloss/deta   (HC0)
+  cov_type='cluster' C = kappa A^-1 M A^-1, M = sum_c g_c g_c^T, g_c = sum_{i in c} m_i s_i x~_i
+                     over the clusters c of ``clusters=`` (one label per row: trial or session
+                     ids), kappa = G/(G-1) (n-1)/(n-k) with G clusters, n = sum m and k kept
+                     coordinates (statsmodels ``cov_type='cluster'`` / Stata), kappa = 1 with
+                     ``cluster_correction=False`` (CR0).  Rows of one cluster need not be
+                     contiguous.  M has rank <= G: a group Wald test with more than G - 1
+                     degrees of freedom is NaN (status 3, one warning).  csrc/cluster.hip;
+                     DESIGN.md §30.
 
 phi = 1 for Poisson, Binomial and NB2 and the Pearson estimate sum m (y - mu)^2 / V(mu) / (n - df)
 for Normal, Gamma and Tweedie, df = tr(A^-1 J); ``scale='pearson'`` forces the estimate on any
@@ -16,9 +24,10 @@ family (quasi-Poisson), a float fixes phi.  A ``NegativeBinomialRegressor(kappa=
 taken at its fitted ``kappa_`` as if that were known: the errors do not carry the uncertainty of
 the dispersion.
 
-Not covered (refused where it can be told): cluster-robust covariance, mixed or non-binary
-designs, models fitted with an L1 or group penalty (naive errors after selection are wrong),
-likelihood-ratio tests, t and F reference distributions.
+Not covered (refused where it can be told): two-way clustering, HAC and leverage-corrected
+(CR2 / CR3) covariances, mixed or non-binary designs, models fitted with an L1 or group penalty
+(naive errors after selection are wrong), likelihood-ratio tests, t and F reference
+distributions.
 """
 from __future__ import annotations
 
@@ -33,7 +42,9 @@ import torch
 from . import engine as E
 from .estimators import NotYetImplementedError
 
-COV_TYPES = {"model": 0, "bayes": 1, "robust": 2}
+# the cov_type sglm_cov_groups is called with ('cluster' hands it its own meat as 'robust' does)
+COV_TYPES = {"model": 0, "bayes": 1, "robust": 2, "cluster": 2}
+ST_RANK = 3     # group status: more degrees of freedom than the clustered meat has rank (G - 1)
 MAX_P = 4096
 # device bytes the float64 P x P buffers of one chunk of fits may take (factor, inverse and its
 # work, Grams, the optional covariance)
@@ -47,7 +58,8 @@ class Inference:
     """Inference of one fitted model (see the module docstring).  ``se`` / ``z`` / ``pvalues``
     are per coefficient (NaN at a coefficient of an all-zero column); the ``group_*`` arrays are
     per group of ``groups`` in the order of ``group_ids`` (None without groups); ``cov`` is the
-    (p + 1) x (p + 1) matrix with the intercept last, when asked for."""
+    (p + 1) x (p + 1) matrix with the intercept last, when asked for; ``n_clusters`` is the
+    number of clusters of ``cov_type='cluster'`` (None for the other types)."""
     coef: np.ndarray
     intercept: float
     se: np.ndarray
@@ -62,6 +74,82 @@ class Inference:
     group_stat: Optional[np.ndarray] = None
     group_pvalue: Optional[np.ndarray] = None
     cov: Optional[np.ndarray] = None
+    # set per instance by cov_type='cluster'; not a dataclass field (the field list is the
+    # constructor's positional order)
+    n_clusters = None
+
+
+@dataclass
+class ClusterRuns:
+    """Row clusters as the kernels take them: ``G`` clusters, the rows cut into ``R`` maximal
+    runs of one cluster (run r = rows roff[r] .. roff[r + 1] - 1) and, unless every cluster is a
+    single run (``coff`` None), the CSR of the runs of each cluster in ascending run order."""
+    G: int
+    R: int
+    roff: np.ndarray
+    coff: Optional[np.ndarray] = None
+    cruns: Optional[np.ndarray] = None
+
+
+def cluster_runs(clusters, n):
+    """``ClusterRuns`` of one label per row (ints, strings, a Series, an index level), through
+    ``np.unique(..., return_inverse=True)``; refuses a wrong length, missing labels and fewer
+    than two clusters (no device)."""
+    import pandas as pd
+    ids = clusters.to_numpy() if isinstance(clusters, (pd.Series, pd.Index)) \
+        else np.asarray(clusters)
+    if ids.ndim == 2 and ids.shape[1] == 1:
+        ids = ids[:, 0]
+    if ids.ndim != 1 or ids.shape[0] != int(n):
+        raise ValueError(f"clusters must hold one label per row: expected length {int(n)}. Got "
+                         f"shape {ids.shape} instead.")
+    if int(n) >= 2 ** 31:
+        raise NotYetImplementedError(f"cov_type='cluster' with n = {int(n)} >= 2^31 rows")
+    if bool(np.any(pd.isna(ids))):
+        raise ValueError("clusters holds NaN or None labels: every row needs a cluster")
+    try:
+        u, inv = np.unique(ids, return_inverse=True)
+    except TypeError as e:
+        raise ValueError(f"clusters holds labels that cannot be ordered ({e})") from None
+    inv = np.asarray(inv).reshape(-1)
+    G = int(u.shape[0])
+    if G < 2:
+        raise ValueError(f"cov_type='cluster' needs at least 2 clusters. Got {G} instead.")
+    starts = np.flatnonzero(np.r_[True, inv[1:] != inv[:-1]])
+    R = int(starts.shape[0])
+    roff = np.r_[starts, int(n)].astype(np.int32)
+    if R == G:
+        return ClusterRuns(G, R, roff)
+    rc = inv[starts]
+    coff = np.r_[0, np.cumsum(np.bincount(rc, minlength=G))].astype(np.int32)
+    return ClusterRuns(G, R, roff, coff, np.argsort(rc, kind="stable").astype(np.int32))
+
+
+def cluster_kappa(G, n, k):
+    """The small-sample factor G/(G-1) (n-1)/(n-k) of statsmodels / Stata."""
+    return float(G) / float(G - 1) * (float(n) - 1.0) / (float(n) - float(k))
+
+
+def check_clusters(cov_type, clusters, n):
+    """The ``ClusterRuns`` of ``clusters`` for cov_type='cluster', None for the other types;
+    refuses one without the other (no device)."""
+    if cov_type == "cluster":
+        if clusters is None:
+            raise ValueError("cov_type='cluster' needs clusters= (one label per row)")
+        return cluster_runs(clusters, n)
+    if clusters is not None:
+        raise ValueError(f"clusters= is read by cov_type='cluster' only. Got cov_type="
+                         f"{cov_type!r} instead.")
+    return None
+
+
+def check_run_bytes(runs, P):
+    """Refuse a run-score buffer [R][P] float64 of a single fit beyond SGLM_INFER_BYTES."""
+    if runs is not None and 8.0 * runs.R * P > INFER_BYTES:
+        raise NotYetImplementedError(
+            f"cov_type='cluster' with {runs.R} runs of rows ({runs.G} clusters, {P} columns): "
+            f"the run scores of one fit take {8.0 * runs.R * P:.3g} bytes > SGLM_INFER_BYTES = "
+            f"{INFER_BYTES:.3g} (sort the rows by cluster, or raise SGLM_INFER_BYTES)")
 
 
 def check_models(models, cov_type="model", scale=None):
@@ -150,10 +238,34 @@ def _row_pass(prob, fam, power, mode, sel, eta, fit_resp_d, fit_mask_d, want_sum
     return Wp, sums
 
 
+def _cluster_meat(prob, runs, s64, st):
+    """M[q] = sum_c g_c g_c^T of the fits of s64 [nb][ld] (their signed scores): one pass over
+    the design's planes for the run scores, the merge of a cluster's runs, the rank-G update."""
+    d = prob.design
+    dev = d.device
+    nb = s64.shape[0]
+    roff_d = torch.from_numpy(runs.roff).to(dev)
+    S = torch.empty((nb, runs.R, d.P), dtype=torch.float64, device=dev)
+    E._lib.call("sglm_cluster_scores", E._p(d.xbits), d.ld, d.P, d.n, E._p(s64), nb,
+                E._p(roff_d), runs.R, E._p(S), st)
+    M64 = torch.empty((nb, d.P, d.P), dtype=torch.float64, device=dev)
+    coff_d = cruns_d = work = None
+    if runs.coff is not None:
+        coff_d = torch.from_numpy(runs.coff).to(dev)
+        cruns_d = torch.from_numpy(runs.cruns).to(dev)
+        work = torch.empty(E._lib.query("sglm_cluster_meat_work_bytes", d.P, nb, runs.G),
+                           dtype=torch.uint8, device=dev)
+    E._lib.call("sglm_cluster_meat", E._p(S), d.P, nb, runs.R, E._p(coff_d), E._p(cruns_d),
+                runs.G, E._p(M64), E._p(work), st)
+    return M64
+
+
 def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, masks,
-                  goff=None, gcols=None, cov_type="model", scale=None, return_cov=False):
+                  goff=None, gcols=None, cov_type="model", scale=None, return_cov=False,
+                  runs=None, cluster_correction=True):
     """Inference of B fits on one problem: per fit its family, power (kappa for NB2), penalty
     ``lam`` (sum scaling), whether it has an intercept, its coefficients, response and mask.
+    ``runs``: the ``ClusterRuns`` of cov_type='cluster' (one for every fit).
     Returns a dict of host arrays: var (B, P), state (B, P), scale, df, n (B), stat / dof /
     status (B, ng) with groups, cov (B, P, P) when asked for."""
     d = prob.design
@@ -161,6 +273,10 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
     P, p, ld, dev = d.P, d.p, d.ld, d.device
     B = len(fams)
     ct = COV_TYPES[cov_type]
+    clustered = cov_type == "cluster"
+    if clustered and runs is None:
+        raise ValueError("cov_type='cluster' needs the runs of its clusters")
+    check_run_bytes(runs if clustered else None, P)
     st = E._stream()
     ng = 0 if goff is None else len(goff) - 1
     goff_d = gcols_d = None
@@ -170,6 +286,8 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
     out = {k: [] for k in ("var", "state", "scale", "df", "n", "stat", "dof", "status", "cov")}
     # P x P float64 buffers alive per fit: U, T, Ainv, the Gram sum (+ M, + cov), f32 H twice
     per = 8 * P * P * (4 + (ct == 2) + bool(return_cov)) + 8 * P * P
+    if clustered:       # the scores, the run scores and the merged cluster scores
+        per += 8 * (ld + runs.R * P + (runs.G * P if runs.coff is not None else 0))
     chunk = max(1, int(INFER_BYTES // per))
     for c0 in range(0, B, chunk):
         sel = np.arange(c0, min(B, c0 + chunk))
@@ -185,7 +303,9 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
         fm = torch.from_numpy(fm_h).to(dev)
         gr = _Grams(prob, fm_h, nb, dev)
         J32 = torch.zeros((nb, P, P), dtype=torch.float32, device=dev)
-        M64 = torch.zeros((nb, P, P), dtype=torch.float64, device=dev) if ct == 2 else None
+        M64 = torch.zeros((nb, P, P), dtype=torch.float64, device=dev) \
+            if ct == 2 and not clustered else None
+        s64 = torch.empty((nb, ld), dtype=torch.float64, device=dev) if clustered else None
         sums = torch.zeros((nb, 2), dtype=torch.float64, device=dev)
         exact = np.zeros(nb, dtype=bool)
         for fam, power in sorted(set((int(fams[k]), float(powers[k])) for k in sel)):
@@ -205,12 +325,22 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
                 J += gr.gram64(Wp[2], fm_h[loc], False, st)
                 J32[loc_d] = J.float()          # the f32 triangle sglm_chol64_factor reads
             sums[loc_d] = s
-            if ct == 2:
+            if clustered:
+                sq = torch.empty((len(loc), ld), dtype=torch.float64, device=dev)
+                slots = loc_d.int()
+                E._lib.call("sglm_infer_scores", int(fam), float(power), d.n, ld, len(loc),
+                            E._p(slots), E._p(eta), E._p(prob.Y), E._p(prob.M), E._p(fr),
+                            E._p(fm), E._p(sq), st)
+                s64[loc_d] = sq
+            elif ct == 2:
                 Wp, _ = _row_pass(prob, fam, power, 1, loc, eta, fr, fm, False, st)
                 Mm = gr.gram64(Wp[0], fm_h[loc], False, st)
                 Mm += gr.gram64(Wp[1], fm_h[loc], False, st)
                 Mm += gr.gram64(Wp[2], fm_h[loc], False, st)
                 M64[loc_d] = Mm + torch.triu(Mm, 1).transpose(1, 2)
+        if clustered:
+            M64 = _cluster_meat(prob, runs, s64, st)
+            del s64
         # A = J + diag(lam on w, 0 on b): float64 factor, then the inverse
         lam = np.array([float(lams[k]) for k in sel])
         fi = np.array([1.0 if icpts[k] else 0.0 for k in sel])
@@ -272,6 +402,17 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
             out[key].append(t.cpu().numpy())
         if return_cov:
             out["cov"].append(cov.cpu().numpy())
+        if clustered:
+            # kappa on the results (sglm_cov_groups is as it was); the meat's rank is <= G
+            # (G - 1 where the g_c sum to zero), so a larger block has no Wald statistic
+            kap = np.array([cluster_kappa(runs.G, nn, kk) if cluster_correction else 1.0
+                            for nn, kk in zip(out["n"][-1], kept.cpu().numpy())])
+            out["var"][-1] = out["var"][-1] * kap[:, None]
+            if return_cov:
+                out["cov"][-1] = out["cov"][-1] * kap[:, None, None]
+            over = (out["dof"][-1] > runs.G - 1) & (out["status"][-1] != 2)
+            out["stat"][-1] = np.where(over, np.nan, out["stat"][-1] / kap[:, None])
+            out["status"][-1] = np.where(over, ST_RANK, out["status"][-1]).astype(np.int32)
     res = {k: np.concatenate(v) for k, v in out.items() if v}
     if not ng:
         for k in ("stat", "dof", "status"):
@@ -279,11 +420,14 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
     return res
 
 
-def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=False):
+def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=False,
+          clusters=None, cluster_correction=True):
     """Inference of one fitted estimator or a list of them (e.g. one per alpha or per
     response) on the design ``X`` they were fitted on: a list of ``Inference`` (one, not a list,
     for a single model).  ``y``: one response vector, or one per model.  ``groups``: one integer
-    id per column (``sglm_ez.event_groups``) for per-group Wald tests."""
+    id per column (``sglm_ez.event_groups``) for per-group Wald tests.  ``clusters``: one label
+    per row (trial or session ids; any labels ``np.unique`` orders) for ``cov_type='cluster'``,
+    shared by every model; ``cluster_correction=False`` drops the small-sample factor (CR0)."""
     import scipy.special
     single = not isinstance(models, (list, tuple))
     models = [models] if single else list(models)
@@ -294,7 +438,9 @@ def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=Fa
     else:
         ys = [np.asarray(y, dtype=np.float64).reshape(-1)]
     resps = list(range(B)) if len(ys) == B and B > 1 else [0] * B
+    runs = check_clusters(cov_type, clusters, ys[0].shape[0])
     p = pairs[0][0].coef_.shape[0]
+    check_run_bytes(runs, E.pad_to(p + 1, E.COL_PAD))
     for m, _ in pairs:
         if m.coef_.shape[0] != p:
             raise ValueError("the models have different numbers of coefficients")
@@ -315,7 +461,11 @@ def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=Fa
                       [o.lam(float(d.n)) for _, o in pairs],
                       [o.fit_intercept for _, o in pairs], [m.coef_ for m, _ in pairs],
                       [m.intercept_ for m, _ in pairs], resps, [0] * B, goff, gcols, cov_type,
-                      scale, return_cov)
+                      scale, return_cov, runs, cluster_correction)
+    if runs is not None and groups is not None and np.any(r["status"] == ST_RANK):
+        warnings.warn(f"{int(np.sum(r['status'] == ST_RANK))} group test(s) have more degrees of "
+                      f"freedom than the {runs.G} clusters leave (G - 1 = {runs.G - 1}): their "
+                      "Wald statistics are NaN", UserWarning, stacklevel=2)
     res = []
     for k, (m, o) in enumerate(pairs):
         var = r["var"][k].copy()
@@ -329,6 +479,8 @@ def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=Fa
                         intercept_se=float(se_all[p]) if o.fit_intercept else float("nan"),
                         z=z, pvalues=pv, scale=float(r["scale"][k]), df=float(r["df"][k]),
                         n=float(r["n"][k]))
+        if runs is not None:
+            inf.n_clusters = runs.G
         if groups is not None:
             stat, dof = r["stat"][k], r["dof"][k].astype(np.int64)
             with np.errstate(invalid="ignore", divide="ignore"):

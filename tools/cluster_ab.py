@@ -1,18 +1,21 @@
-"""What inference costs next to the fit it follows, on the C3-size workload.
+"""What cluster-robust inference costs next to the fit it follows and next to the 'robust' and
+'model' covariances, on the C3-size workload.
 
 Shape: 100k rows x 500 predictors (25 events x 20 lags, sglm_hip.synth), a device-resident lag
-design, Poisson fits at 1 and at 20 alphas (logspace(-4, 1)), one GPU.
+design, Poisson fits at 1 and at 20 alphas (logspace(-4, 1)), one GPU; --trials contiguous trials
+of equal length are the clusters (1000 of 100 rows by default).
 
 For each model count, interleaved in one process (alternating order): the fits alone
 (engine.irls) and the fits followed by inference.infer_problem with per-event Wald groups, for
-each cov_type; median of --runs timed runs after --warmup untimed ones, each a host clock around
+'model', 'robust' and 'cluster'; median of --runs timed runs after --warmup untimed ones, each a host clock around
 work that ends in a device synchronise.  A last instrumented run per (count, cov_type) puts
-device events around every C ABI call inference makes and reports the time per entry point.
+device events around every C ABI call inference makes and reports the time per entry point;
+"cluster_kernels_ms" is the split between the three entry points of csrc/cluster.hip.
 There is no bar: the output states the cost of inference as a multiple of the fit.
 
 Writes one JSON file.
 
-    python tools/infer_ab.py --out profiles/infer_ab.json
+    python tools/infer_ab.py --out profiles/cluster_ab.json
 """
 import argparse
 import json
@@ -30,9 +33,10 @@ def main():
     ap.add_argument("--rows", type=int, default=100_000)
     ap.add_argument("--events", type=int, default=25)
     ap.add_argument("--L", type=int, default=10, help="lags -L .. L-1")
+    ap.add_argument("--trials", type=int, default=1000)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infer_ab.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cluster_ab.json"))
     a = ap.parse_args()
     for q in (ROOT, os.path.join(ROOT, "sabatinilab-glm_amd")):
         if q not in sys.path:
@@ -49,6 +53,9 @@ def main():
     cols = np.arange(p)
     ev = cols % a.events if design.lag is not None and design.lag.layout == 0 else cols // (2 * a.L)
     ids, goff, gcols, sizes = inference.group_lists(ev, p)
+    trial = np.arange(n) // -(-n // a.trials)
+    runs = inference.cluster_runs(trial, n)
+    cov_types = ("model", "robust", "cluster")
 
     def fit(alphas):
         reqs = [E.FitReq(E.FAM_TWEEDIE_LOG, 1.0, float(al) * n, 0, 0) for al in alphas]
@@ -60,7 +67,7 @@ def main():
         return inference.infer_problem(
             prob, [r.family for r in reqs], [r.power for r in reqs], [r.lam for r in reqs],
             [True] * B, [r.coef for r in res], [r.intercept for r in res], [0] * B, [0] * B,
-            goff, gcols, cov_type)
+            goff, gcols, cov_type, runs=runs if cov_type == "cluster" else None)
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -70,11 +77,11 @@ def main():
         return time.perf_counter() - t0, out
 
     out = {"shape": {"rows": int(n), "p": int(p), "P": int(design.P), "events": a.events,
-                     "lags": 2 * a.L, "groups": int(len(ids)), "group_columns": int(sizes.max())},
+                     "lags": 2 * a.L, "groups": int(len(ids)), "group_columns": int(sizes.max()),
+                     "clusters": int(runs.G), "runs_of_rows": int(runs.R)},
            "device": torch.cuda.get_device_name(0), "runs": a.runs, "warmup": a.warmup,
            "family": "poisson", "models": {}}
     real_call = _lib.call
-    cov_types = [c for c in inference.COV_TYPES if c != "cluster"]   # tools/cluster_ab.py times it
     for count in (1, 20):
         alphas = np.logspace(-4, 1, count) if count > 1 else np.array([1e-3])
         variants = ["fit"] + [f"fit+{c}" for c in cov_types]
@@ -123,6 +130,9 @@ def main():
                 k[1] += e0.elapsed_time(e1)
             rec["entry_points_ms"][c] = {k: {"calls": v[0], "ms": round(v[1], 3)}
                                          for k, v in per.items()}
+        rec["cluster_kernels_ms"] = {k: v["ms"] for k, v in rec["entry_points_ms"]["cluster"].items()
+                                     if k in ("sglm_infer_scores", "sglm_cluster_scores",
+                                              "sglm_cluster_meat")}
         out["models"][str(count)] = rec
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
