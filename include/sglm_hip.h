@@ -1191,6 +1191,38 @@ int sglm_cluster_meat(const double* S, int32_t P, int32_t B, int32_t R, const in
                       const int32_t* cruns, int32_t G, double* Mout, void* work,
                       sglm_stream_t stream);
 
+/* --- pointwise bands of fitted traces: eta = x~^T beta and v = x~^T C x~ per row ------------
+ * (csrc/predict.hip; statsmodels get_prediction().summary_frame(): mean_se^2 on the link scale.)
+ * Both read the row-major planes rbits [P/64][ld] x 8 B of a 0/1 design (sglm_pack_bits_t /
+ * sglm_lag_bits), beta float64 [B][P], the covariance cov float64 [B][P][P] of sglm_cov_groups
+ * (symmetric: only entries j <= k are read) and state [B][P] of sglm_chol64_factor.  The nr
+ * evaluated rows are rows[k] (DEVICE int32 [nr], read back and validated on the host:
+ * 0 <= rows[k] < n; any order, repeats allowed) or 0 .. nr - 1 (rows NULL, nr <= n).  Columns
+ * >= p of the planes and rows >= n are never read as data.
+ * sglm_predict_rows: eta[f][k] = sum of beta[f][j] over the set columns j < p of the row, plus
+ *   beta[f][p] when icpt[f] != 0 (DEVICE int32 [B]); var[f][k] = sum_{j,k' in S} C_jk' over that
+ *   set S (the intercept coordinate p included with icpt), as diagonal + 2 upper.  One wave per
+ *   (row, fit): the m (m + 1) / 2 terms in ascending (j, k') order are dealt to the 64 lanes
+ *   round-robin, each lane adds its terms in that order, a fixed butterfly adds the lanes.
+ * sglm_predict_groups: for the groups of a CSR over the p coefficients (sglm_cov_groups'
+ *   conventions and host validation), geta[f][g][k] = x_g^T w_g and gvar[f][g][k] =
+ *   x_g^T C_gg x_g (float64 [B][ng][nr]), no intercept; C_gg in LDS, the terms of a row added in
+ *   ascending order.  A row with no set bit in the group gets exactly 0 and 0.  A group of more
+ *   than sglm_cov_groups_kmax() = 64 columns gets NaN in both.
+ * All sums are float64 in an order that depends on the row's bits alone (not on the launch, the
+ * batch or the row list); no atomics; a repeated call returns the same bits.  A row with a set
+ * bit at a coordinate with state != 0 gets var = NaN.
+ * P % 64 == 0, p < P <= 4096, n <= ld < 2^31, nr < 2^31, B <= 65535. */
+int sglm_predict_rows(const uint32_t* rbits, int64_t ld, int32_t P, int32_t p, int64_t n,
+                      const int32_t* rows, int64_t nr, const double* beta, const double* cov,
+                      const uint8_t* state, const int32_t* icpt, int32_t B, double* eta,
+                      double* var, sglm_stream_t stream);
+int sglm_predict_groups(const uint32_t* rbits, int64_t ld, int32_t P, int32_t p, int64_t n,
+                        const int32_t* rows, int64_t nr, const double* beta, const double* cov,
+                        const uint8_t* state, int32_t B, const int32_t* goff,
+                        const int32_t* gcols, int32_t ng, double* geta, double* gvar,
+                        sglm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,17 @@ class GLM():
             X = host_matrix(X)
         return self.model.inference(X, y, **kw)
 
+    def predict_bands(self, X, y, X_new=None, **kw):
+        """Pointwise confidence bands of the fitted trace on the rows of ``X_new`` (default: the
+        design ``X`` the model was fitted on) and, with ``groups``, of each group's share of the
+        predictor (``sglm_hip.inference.predict_bands``; keywords ``rows``, ``groups``, ``level``
+        and ``inference``'s ``cov_type``, ``scale``, ``clusters``, ``cluster_correction``)."""
+        if type(X) == pd.DataFrame:
+            X = host_matrix(X)
+        if type(X_new) == pd.DataFrame:
+            X_new = host_matrix(X_new)
+        return self.model.predict_bands(X, y, X_new, **kw)
+
     def get_residuals(self, X: Union[np.ndarray, pd.DataFrame],
                       y: Union[np.ndarray, pd.Series]) -> Tuple[np.ndarray, np.ndarray]:
         residuals = (y - self.predict(X))

@@ -233,6 +233,52 @@ def kernel_bands(X, y, glm, level=0.95, **kw):
                          "hi": r.coef + zq * r.se}, index=pd.Index(list(X.columns), name="column"))
 
 
+def _band_index(X, X_new, rows):
+    """The index of the evaluated rows: the evaluated frame's own, or a RangeIndex."""
+    from sglm_hip import inference
+    Xe = X if X_new is None else X_new
+    n = Xe.shape[0]
+    index = Xe.index if hasattr(Xe, "index") else pd.RangeIndex(n)
+    idx = inference.normalize_rows(rows, n)
+    return index if idx is None else index[idx]
+
+
+def fitted_bands(X, y, glm, X_new=None, level=0.95, **kw):
+    """The fitted trace of ``glm`` with its pointwise confidence band on the rows of ``X_new``
+    (a frame with X's columns, e.g. holdout rows; default ``X``, the frame the model was fitted
+    on): a DataFrame indexed like the evaluated rows with ``mean``, ``mean_se``, ``lo``, ``hi``
+    (the inverse link of eta -+ z_level eta_se, inside the mean's range), ``eta`` and ``eta_se``
+    -- statsmodels' ``get_prediction().summary_frame()``.  The covariance always comes from
+    ``(X, y)``.  ``kw``: ``rows`` and ``event_wald``'s ``cov_type``, ``scale``, ``clusters``.
+    Pointwise bands of the mean, not simultaneous and not prediction intervals."""
+    from sglm_hip import inference
+    index = _band_index(X, X_new, kw.get("rows"))
+    r = inference.predict_bands(X, y, glm, X_new, level=level, **kw)
+    return pd.DataFrame({"mean": r.mean, "mean_se": r.mean_se, "lo": r.lo, "hi": r.hi,
+                         "eta": r.eta, "eta_se": r.eta_se}, index=index)
+
+
+def event_contributions(X, y, glm, X_new=None, rows=None, level=0.95, **kw):
+    """Every event kernel's share X_g w_g of the fitted predictor with its pointwise band, on
+    the rows ``rows`` (a slice or index array; default all) of ``X_new`` (default ``X``): a
+    DataFrame indexed like the evaluated rows whose columns are a MultiIndex (event, 'eta' |
+    'se' | 'lo' | 'hi') over ``event_groups``'s groups, on the link scale.  The events' ``eta``
+    columns plus the intercept sum to ``fitted_bands``' ``eta``.  ``kw`` as ``fitted_bands``."""
+    from sglm_hip import inference
+    index = _band_index(X, X_new, rows)
+    r = inference.predict_bands(X, y, glm, X_new, rows=rows, groups=event_groups(X), level=level,
+                                **kw)
+    names = list(dict.fromkeys(_event_bases(X)))
+    cols = {}
+    for g, name in enumerate(names):
+        for key, arr in (("eta", r.group_eta), ("se", r.group_se), ("lo", r.group_lo),
+                         ("hi", r.group_hi)):
+            cols[(name, key)] = arr[g]
+    out = pd.DataFrame(cols, index=index)
+    out.columns = pd.MultiIndex.from_tuples(list(cols), names=["event", None])
+    return out
+
+
 def reduce_cv_result(r, drop, glm_kwargs, model_name):
     """One parameter's grid result dict (full length p, zeros on the dropped columns ``drop``)
     as the reference's loop over column-deleted frames reports it: coefficients of the kept

@@ -216,6 +216,10 @@ SIGNATURES = {
     "sglm_cluster_scores": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     "sglm_cluster_meat_work_bytes": (_sz, [_i32, _i32, _i32]),
     "sglm_cluster_meat": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "sglm_predict_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                    _i32, _vp, _vp, _vp]),
+    "sglm_predict_groups": (C.c_int, [_vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _i32,
+                                      _vp, _vp, _i32, _vp, _vp, _vp]),
 }
 
 

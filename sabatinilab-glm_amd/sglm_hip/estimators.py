@@ -306,6 +306,15 @@ class _EngineRegressor:
         from . import inference
         return inference.infer(X, y, self, **kw)
 
+    def predict_bands(self, X, y, X_new=None, **kw):
+        """Pointwise confidence bands of this fitted model's trace (``eta``, ``mean``, their
+        standard errors, ``lo`` / ``hi``) on the rows of ``X_new`` (default: the design ``X`` it
+        was fitted on), with ``groups=`` each group's share of the predictor and its band:
+        ``inference.predict_bands(X, y, self, X_new, **kw)`` (``rows``, ``level`` and
+        ``inference``'s ``cov_type``, ``scale``, ``clusters``)."""
+        from . import inference
+        return inference.predict_bands(X, y, self, X_new, **kw)
+
     def score(self, X, y, sample_weight=None):
         """R^2 (Gaussian estimators, sklearn RegressorMixin.score)."""
         y = np.asarray(y, dtype=np.float64).reshape(-1)

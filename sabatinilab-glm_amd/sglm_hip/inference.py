@@ -24,6 +24,10 @@ family (quasi-Poisson), a float fixes phi.  A ``NegativeBinomialRegressor(kappa=
 taken at its fitted ``kappa_`` as if that were known: the errors do not carry the uncertainty of
 the dispersion.
 
+``predict_bands`` carries C to the fitted trace: per evaluated row eta = x~^T beta with the
+standard error sqrt(x~^T C x~), the mean and its band through the inverse link, and per column
+group the share X_g w_g with sqrt(x_g^T C_gg x_g) (csrc/predict.hip).
+
 Not covered (refused where it can be told): two-way clustering, HAC and leverage-corrected
 (CR2 / CR3) covariances, mixed or non-binary designs, models fitted with an L1 or group penalty
 (naive errors after selection are wrong), likelihood-ratio tests, t and F reference
@@ -262,12 +266,18 @@ def _cluster_meat(prob, runs, s64, st):
 
 def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, masks,
                   goff=None, gcols=None, cov_type="model", scale=None, return_cov=False,
-                  runs=None, cluster_correction=True):
+                  runs=None, cluster_correction=True, _on_chunk=None, _extra_bytes=0):
     """Inference of B fits on one problem: per fit its family, power (kappa for NB2), penalty
     ``lam`` (sum scaling), whether it has an intercept, its coefficients, response and mask.
     ``runs``: the ``ClusterRuns`` of cov_type='cluster' (one for every fit).
     Returns a dict of host arrays: var (B, P), state (B, P), scale, df, n (B), stat / dof /
-    status (B, ng) with groups, cov (B, P, P) when asked for."""
+    status (B, ng) with groups, cov (B, P, P) when asked for.
+    ``_on_chunk(sel, beta_d, cov, state, kap)`` (internal: predict_bands' row pass) is called once
+    per chunk of fits ``sel`` with the chunk's device coefficients [nb][P], covariance
+    [nb][P][P] and state [nb][P] and the host factors ``kap`` [nb] the clustered covariance is
+    still to be multiplied by (None for the other types); the covariance is then formed on the
+    device whether or not ``return_cov`` copies it.  ``_extra_bytes``: device bytes per fit the
+    callback allocates, counted into the chunk size."""
     d = prob.design
     check_design(d)
     P, p, ld, dev = d.P, d.p, d.ld, d.device
@@ -285,7 +295,8 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
         gcols_d = torch.from_numpy(np.asarray(gcols, dtype=np.int32)).to(dev)
     out = {k: [] for k in ("var", "state", "scale", "df", "n", "stat", "dof", "status", "cov")}
     # P x P float64 buffers alive per fit: U, T, Ainv, the Gram sum (+ M, + cov), f32 H twice
-    per = 8 * P * P * (4 + (ct == 2) + bool(return_cov)) + 8 * P * P
+    want_cov = bool(return_cov) or _on_chunk is not None
+    per = 8 * P * P * (4 + (ct == 2) + want_cov) + 8 * P * P + int(_extra_bytes)
     if clustered:       # the scores, the run scores and the merged cluster scores
         per += 8 * (ld + runs.R * P + (runs.G * P if runs.coff is not None else 0))
     chunk = max(1, int(INFER_BYTES // per))
@@ -393,7 +404,7 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
         stat = torch.zeros((nb, max(ng, 1)), dtype=torch.float64, device=dev)
         dof = torch.zeros((nb, max(ng, 1)), dtype=torch.int32, device=dev)
         status = torch.zeros((nb, max(ng, 1)), dtype=torch.int32, device=dev)
-        cov = torch.zeros((nb, P, P), dtype=torch.float64, device=dev) if return_cov else None
+        cov = torch.zeros((nb, P, P), dtype=torch.float64, device=dev) if want_cov else None
         E._lib.call("sglm_cov_groups", E._p(Ainv), P, p, None, E._p(state), E._p(M64), ct, nb,
                     E._p(lam_d), E._p(phi), E._p(beta_d), E._p(goff_d), E._p(gcols_d), ng,
                     E._p(var), E._p(stat), E._p(dof), E._p(status), E._p(cov), st)
@@ -402,6 +413,7 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
             out[key].append(t.cpu().numpy())
         if return_cov:
             out["cov"].append(cov.cpu().numpy())
+        kap = None
         if clustered:
             # kappa on the results (sglm_cov_groups is as it was); the meat's rank is <= G
             # (G - 1 where the g_c sum to zero), so a larger block has no Wald statistic
@@ -413,6 +425,8 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
             over = (out["dof"][-1] > runs.G - 1) & (out["status"][-1] != 2)
             out["stat"][-1] = np.where(over, np.nan, out["stat"][-1] / kap[:, None])
             out["status"][-1] = np.where(over, ST_RANK, out["status"][-1]).astype(np.int32)
+        if _on_chunk is not None:
+            _on_chunk(sel, beta_d, cov, state, kap)
     res = {k: np.concatenate(v) for k, v in out.items() if v}
     if not ng:
         for k in ("stat", "dof", "status"):
@@ -420,15 +434,10 @@ def infer_problem(prob, fams, powers, lams, icpts, coefs, intercepts, resps, mas
     return res
 
 
-def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=False,
-          clusters=None, cluster_correction=True):
-    """Inference of one fitted estimator or a list of them (e.g. one per alpha or per
-    response) on the design ``X`` they were fitted on: a list of ``Inference`` (one, not a list,
-    for a single model).  ``y``: one response vector, or one per model.  ``groups``: one integer
-    id per column (``sglm_ez.event_groups``) for per-group Wald tests.  ``clusters``: one label
-    per row (trial or session ids; any labels ``np.unique`` orders) for ``cov_type='cluster'``,
-    shared by every model; ``cluster_correction=False`` drops the small-sample factor (CR0)."""
-    import scipy.special
+def _resolve_models(y, models, groups, cov_type, scale, clusters):
+    """The host-side checks infer and predict_bands share (no device): (single, (model,
+    objective) pairs, responses, response slot per model, ClusterRuns or None, p, and the group
+    ids / goff / gcols / sizes of ``groups`` or four Nones)."""
     single = not isinstance(models, (list, tuple))
     models = [models] if single else list(models)
     pairs = check_models(models, cov_type, scale)
@@ -444,13 +453,35 @@ def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=Fa
     for m, _ in pairs:
         if m.coef_.shape[0] != p:
             raise ValueError("the models have different numbers of coefficients")
-    ids = goff = gcols = None
+    ids = goff = gcols = sizes = None
     if groups is not None:
         ids, goff, gcols, sizes = group_lists(groups, p)
+    return single, pairs, ys, resps, runs, p, ids, goff, gcols, sizes
+
+
+def _resolve_design(pairs, X, p):
+    """The resident design of ``X`` through the models' ``_design``, refused as ``check_design``
+    refuses it."""
     d = pairs[0][0]._design(X)
     if d.p != p:
         raise ValueError(f"X has {d.p} features, but the models are expecting {p} features")
     check_design(d)
+    return d
+
+
+def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=False,
+          clusters=None, cluster_correction=True):
+    """Inference of one fitted estimator or a list of them (e.g. one per alpha or per
+    response) on the design ``X`` they were fitted on: a list of ``Inference`` (one, not a list,
+    for a single model).  ``y``: one response vector, or one per model.  ``groups``: one integer
+    id per column (``sglm_ez.event_groups``) for per-group Wald tests.  ``clusters``: one label
+    per row (trial or session ids; any labels ``np.unique`` orders) for ``cov_type='cluster'``,
+    shared by every model; ``cluster_correction=False`` drops the small-sample factor (CR0)."""
+    import scipy.special
+    single, pairs, ys, resps, runs, p, ids, goff, gcols, sizes = _resolve_models(
+        y, models, groups, cov_type, scale, clusters)
+    B = len(pairs)
+    d = _resolve_design(pairs, X, p)
     if groups is not None:
         kmax = E._lib.query("sglm_cov_groups_kmax")
         if np.any(sizes > kmax):
@@ -493,3 +524,192 @@ def infer(X, y, models, groups=None, cov_type="model", scale=None, return_cov=Fa
         res.append(inf)
     return res[0] if single else res
 
+
+
+# ------------------------------------------------------------------------------ fitted traces
+@dataclass
+class PredictionBands:
+    """Pointwise bands of one fitted model's trace over the evaluated rows (``predict_bands``;
+    statsmodels ``get_prediction().summary_frame()``).  ``eta`` / ``eta_se``: the linear
+    predictor and its standard error sqrt(x~^T C x~); ``mean`` the inverse link of eta,
+    ``mean_se`` the delta-method |dmu/deta| eta_se, ``lo`` / ``hi`` the inverse link of
+    eta -+ z_level eta_se.  With groups, ``group_eta`` / ``group_se`` / ``group_lo`` /
+    ``group_hi`` (ng x rows, link scale, no intercept) are each group's share X_g w_g of eta in
+    the order of ``group_ids`` (NaN for a group of more than 64 columns)."""
+    eta: np.ndarray
+    eta_se: np.ndarray
+    mean: np.ndarray
+    mean_se: np.ndarray
+    lo: np.ndarray
+    hi: np.ndarray
+    level: float
+    group_ids: Optional[np.ndarray] = None
+    group_eta: Optional[np.ndarray] = None
+    group_se: Optional[np.ndarray] = None
+    group_lo: Optional[np.ndarray] = None
+    group_hi: Optional[np.ndarray] = None
+
+
+def normalize_rows(rows, n):
+    """``rows`` of ``predict_bands`` as an int32 index array into the n evaluated rows (None:
+    every row): a slice, or integers in [0, n) in any order, repeats allowed (no device)."""
+    if rows is None:
+        return None
+    if isinstance(rows, slice):
+        return np.ascontiguousarray(np.arange(int(n), dtype=np.int32)[rows])
+    idx = np.asarray(rows)
+    if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+        raise ValueError(f"rows must be a slice or a 1-D array of integer row indices. Got "
+                         f"shape {idx.shape}, dtype {idx.dtype} instead.")
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= int(n)):
+        raise ValueError(f"rows must lie in [0, {int(n)}). Got a range of [{int(idx.min())}, "
+                         f"{int(idx.max())}] instead.")
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def level_quantile(level):
+    """z of a two-sided normal band at ``level``; refuses a level outside (0, 1)."""
+    import scipy.special
+    if isinstance(level, (str, bytes)) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must lie in (0, 1). Got {level!r} instead.")
+    return float(np.sqrt(2.0) * scipy.special.erfinv(float(level)))
+
+
+def link_bands(family, eta, se, zq):
+    """(mean, mean_se, lo, hi) of a predictor and its standard error: the inverse link of eta
+    and of eta -+ zq se (so the band stays inside the mean's range), mean_se = |dmu/deta| se;
+    host float64, the logistic function from exp(-|eta|) (no overflow)."""
+    from .estimators import sigmoid_np
+    eta, se = np.asarray(eta, dtype=np.float64), np.asarray(se, dtype=np.float64)
+    a, b = eta - zq * se, eta + zq * se
+    if family == E.FAM_BINOMIAL_LOGIT:
+        e = np.exp(-np.abs(eta))
+        return sigmoid_np(eta), e / (1.0 + e) ** 2 * se, sigmoid_np(a), sigmoid_np(b)
+    if family in (E.FAM_TWEEDIE_LOG, E.FAM_NB2_LOG):
+        mu = np.exp(eta)
+        return mu, mu * se, np.exp(a), np.exp(b)
+    return eta.copy(), se.copy(), a, b
+
+
+def check_new_design(X_new, p):
+    """The host-side refusals of ``X_new`` (no device): another column count, entries that are
+    not 0/1 (a device-resident lagged frame is 0/1 by construction).  Returns its row count."""
+    from .estimators import _as2d
+    from .lagframe import LagFrame
+    Xn = _as2d(X_new)
+    if Xn.shape[1] != p:
+        raise ValueError(f"X_new has {Xn.shape[1]} features, but the models are expecting {p} "
+                         "features")
+    if not isinstance(Xn, LagFrame) and not bool(np.all((Xn == 0) | (Xn == 1))):
+        raise ValueError("X_new must be a 0/1 design with the columns of X: it holds entries "
+                         "that are neither 0 nor 1")
+    return int(Xn.shape[0])
+
+
+def check_band_bytes(nr, ng):
+    """Refuse an output of a single fit (eta and variance of the trace and of ng groups over nr
+    rows, float64) beyond SGLM_INFER_BYTES; returns its bytes."""
+    nbytes = 16.0 * nr * (1 + ng)
+    if nbytes > INFER_BYTES:
+        raise NotYetImplementedError(
+            f"predict_bands over {nr} rows and {ng} groups: the output of one fit takes "
+            f"{nbytes:.3g} bytes > SGLM_INFER_BYTES = {INFER_BYTES:.3g} (pass rows=, or raise "
+            "SGLM_INFER_BYTES)")
+    return int(nbytes)
+
+
+def predict_bands(X, y, models, X_new=None, rows=None, groups=None, level=0.95,
+                  cov_type="model", scale=None, clusters=None, cluster_correction=True):
+    """Pointwise confidence bands of the fitted trace of one fitted estimator or a list of them
+    (as ``infer``: one per alpha or per response on one resident design): a ``PredictionBands``
+    each.  The covariance C is ``infer``'s, from ``(X, y)`` the models were fitted on; the trace
+    is evaluated on ``X_new`` (a 0/1 design with the same columns, e.g. holdout rows; default
+    ``X``), on its rows ``rows`` (a slice or an index array, any order, repeats allowed; default
+    all).  ``groups``: one integer id per column (``sglm_ez.event_groups``) for each group's
+    share of the predictor with its own band.  C and the coefficients stay on the device
+    (csrc/predict.hip); the fits are chunked against SGLM_INFER_BYTES with their
+    outputs counted in, and an output of one fit beyond it is refused (pass ``rows``).
+    Pointwise, normal-theory bands of the mean: not simultaneous, not prediction intervals."""
+    zq = level_quantile(level)
+    single, pairs, ys, resps, runs, p, ids, goff, gcols, sizes = _resolve_models(
+        y, models, groups, cov_type, scale, clusters)
+    B = len(pairs)
+    n_eval = ys[0].shape[0] if X_new is None else check_new_design(X_new, p)
+    idx = normalize_rows(rows, n_eval)
+    nr = n_eval if idx is None else int(idx.shape[0])
+    ng = 0 if groups is None else len(goff) - 1
+    out_bytes = check_band_bytes(nr, ng)
+    d = _resolve_design(pairs, X, p)
+    dn = d
+    if X_new is not None:
+        dn = pairs[0][0]._design(X_new)
+        if dn.xbits is None or dn.cont is not None:
+            raise ValueError("X_new must be a 0/1 design with the columns of X")
+        check_design(dn)
+    if dn.n != n_eval:
+        raise ValueError(f"Found input variables with inconsistent numbers of samples: "
+                         f"[{dn.n}, {n_eval}]")
+    if dn.rbits is None:
+        raise NotYetImplementedError("predict_bands on a design without row-major bit planes")
+    if groups is not None:
+        kmax = E._lib.query("sglm_cov_groups_kmax")
+        if np.any(sizes > kmax):
+            warnings.warn(f"{int(np.sum(sizes > kmax))} group(s) have more than {kmax} columns: "
+                          "their traces are NaN", UserWarning, stacklevel=2)
+    dev = dn.device
+    eta = np.zeros((B, nr))
+    var = np.zeros((B, nr))
+    geta = np.zeros((B, ng, nr)) if ng else None
+    gvar = np.zeros((B, ng, nr)) if ng else None
+    goff_d = gcols_d = None
+    if ng:
+        goff_d = torch.from_numpy(np.asarray(goff, dtype=np.int32)).to(dev)
+        gcols_d = torch.from_numpy(np.asarray(gcols, dtype=np.int32)).to(dev)
+    idx_d = None if idx is None else torch.from_numpy(idx).to(dev)
+
+    def row_pass(sel, beta_d, cov, state, kap):
+        # one launch over all nr rows: the chunk of fits already counts its outputs
+        # (_extra_bytes), and one fit's output fits SGLM_INFER_BYTES (check_band_bytes)
+        nb = len(sel)
+        st = E._stream()
+        ic = torch.tensor([1 if pairs[k][1].fit_intercept else 0 for k in sel],
+                          dtype=torch.int32, device=dev)
+        e_d = torch.empty((nb, nr), dtype=torch.float64, device=dev)
+        v_d = torch.empty((nb, nr), dtype=torch.float64, device=dev)
+        E._lib.call("sglm_predict_rows", E._p(dn.rbits), dn.ld, dn.P, dn.p, dn.n, E._p(idx_d),
+                    nr, E._p(beta_d), E._p(cov), E._p(state), E._p(ic), nb, E._p(e_d),
+                    E._p(v_d), st)
+        eta[sel] = e_d.cpu().numpy()
+        v = v_d.cpu().numpy()
+        var[sel] = v if kap is None else v * kap[:, None]
+        if ng:
+            ge_d = torch.empty((nb, ng, nr), dtype=torch.float64, device=dev)
+            gv_d = torch.empty((nb, ng, nr), dtype=torch.float64, device=dev)
+            E._lib.call("sglm_predict_groups", E._p(dn.rbits), dn.ld, dn.P, dn.p, dn.n,
+                        E._p(idx_d), nr, E._p(beta_d), E._p(cov), E._p(state), nb,
+                        E._p(goff_d), E._p(gcols_d), ng, E._p(ge_d), E._p(gv_d), st)
+            geta[sel] = ge_d.cpu().numpy()
+            gv = gv_d.cpu().numpy()
+            gvar[sel] = gv if kap is None else gv * kap[:, None, None]
+
+    if nr:
+        prob = E.Problem(d, ys, [np.ones(d.n, np.uint8)])
+        infer_problem(prob, [o.family for _, o in pairs], [o.power for _, o in pairs],
+                      [o.lam(float(d.n)) for _, o in pairs],
+                      [o.fit_intercept for _, o in pairs], [m.coef_ for m, _ in pairs],
+                      [m.intercept_ for m, _ in pairs], resps, [0] * B, None, None, cov_type,
+                      scale, False, runs, cluster_correction, _on_chunk=row_pass,
+                      _extra_bytes=out_bytes)
+    res = []
+    for k, (_, o) in enumerate(pairs):
+        with np.errstate(invalid="ignore"):
+            se = np.sqrt(var[k])
+            mean, mean_se, lo, hi = link_bands(o.family, eta[k], se, zq)
+            pb = PredictionBands(eta=eta[k], eta_se=se, mean=mean, mean_se=mean_se, lo=lo, hi=hi,
+                                 level=float(level))
+            if groups is not None:
+                gse = np.sqrt(gvar[k])
+                pb.group_ids, pb.group_eta, pb.group_se = ids, geta[k], gse
+                pb.group_lo, pb.group_hi = geta[k] - zq * gse, geta[k] + zq * gse
+        res.append(pb)
+    return res[0] if single else res
