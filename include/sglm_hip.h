@@ -133,6 +133,13 @@ int sglm_gemv_eta(const void* X, int32_t xtype, int64_t ld, int32_t P, int64_t n
  * step's predictor update, fused), then the link on the updated eta.
  * W may be NULL: the weights are then not stored (eta, R and Rp are what they are with W
  * given); sglm_link_weights writes them later from the eta this call leaves behind.
+ * families SGLM_FAM_SQUARED and SGLM_FAM_TWEEDIE_LOG: R and W in f32 from the fast exponential
+ * (v_exp_f32 of x log2 e, relative error about (2 |x| + 4) 2^-24 at the argument x) of eta
+ * (power 1), -eta (power 2), or (2 - power) eta and (1 - power) eta; W >= 0 for y >= 0 and
+ * 1 <= power <= 2.  Every output is finite for |eta| <= 80 with 0 <= y <= 5 and mask values
+ * <= 2 (held to float64 row by row on that range: tests/test_gpu_tweedie_rows.py).  Past it the
+ * exponential overflows (|x| > 88), and power 2, or a general power with y = 0, can form
+ * 0 * inf: no promise is made there; the step control keeps fits away from it.
  * family SGLM_FAM_BINOMIAL_LOGIT: R = M (sigma(eta) - y), W = M sigma (1 - sigma) as
  * e / (1 + e)^2 with e = exp(-|eta|) (no overflow, W >= 0; W underflows to 0 past |eta| ~ 87).
  * family SGLM_FAM_NB2_LOG (kappa = power): R = M (mu - y) / (1 + kappa mu), W = M mu (1 + kappa y)
@@ -650,6 +657,10 @@ int sglm_nb2_kappa_sums(int64_t n, int64_t ld, int32_t nfit, const int32_t* slot
  * factor, l(t) - l(0) = (y + 1/kappa) log1p(q (exp(t deta) - 1)) - y t deta with
  * q = sigma(eta + ln kappa), the same |deta| > 3 guard, the same guarantees.
  * Every other (family, power, T, t) sums float64 losses per trial.
+ * SGLM_FAM_SQUARED and SGLM_FAM_TWEEDIE_LOG: every output is finite for |eta + t deta| <= 83.5
+ * with 0 <= y <= 5 and mask values <= 2 (|eta| <= 80, |deta| <= 3.5; the Poisson differences
+ * form mu in f32, the rest is float64), the range tests/test_gpu_tweedie_rows.py covers; no
+ * promise is made past the f32 overflow of exp(eta) (|eta| > 88).
  * The sums are two-level and deterministic: block partials per 8192-row chunk, then one wave per
  * output sums the chunks in a fixed order. */
 size_t sglm_rowsum_work_bytes(int32_t B, int32_t T, int64_t n);
